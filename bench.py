@@ -8,7 +8,11 @@ resolve, TAA (with the fused velocity history), AgX tone mapping into an RGBA8 f
 are resident in HBM before timing starts. N GPUs: one process per GPU, each renders its own camera
 (frame-per-GPU sharding, SURVEY.md §8e, weak scaling); value = frames of all ranks / max rank time.
 
-Prints ONE JSON line on rank 0. See DESIGN.md §6 for the roofline accounting.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times --steps frames and prints the headline
+(value, ms_per_step, the configuration); --dump-outputs DIR also writes the last timed frame's images. --full adds
+what takes runs of its own after the timed frames: the serial per-pass loop (ms_per_pass, ms_per_group), the
+unfused groups, the roofline of the north-star kernels (with their pass events on during the timed frames) and
+the CPU baseline. See DESIGN.md §6 for the roofline accounting.
 """
 from __future__ import annotations
 
@@ -294,6 +298,35 @@ def build_inputs(config, scene_name, W, H, rank, device, mips=True, output_forma
     return g, gb, shadow, noise, sc, fr
 
 
+DUMP_SAMPLE_PIXELS = 1 << 20   # per image: 3 images x 2^20 pixels x RGBA f32 = 48 MiB
+DUMP_SAMPLE_SEED = 0xD0
+
+
+def dump_outputs(dirname, fr, renderer, rank=0):
+    """--dump-outputs: what the frame path left for its caller after the last timed frame, as float32 / float64 .npy
+    files: the tone-mapped framebuffer (`output`), the HDR composition colour (`color`), the TAA-resolved history
+    (`resolved`) and the exposure (the histogram's bins are cleared by the resolve). Images larger than
+    DUMP_SAMPLE_PIXELS are written as the same seeded sample of their pixels (sorted flat indices, one (n, 4) row per
+    pixel) in every run. Rank r > 0 writes <name>.rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    if fr["output"].is_cuda:
+        torch.cuda.synchronize()
+    H, W = fr["output"].shape[:2]
+    P = H * W
+    idx = None
+    if P > DUMP_SAMPLE_PIXELS:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(P, DUMP_SAMPLE_PIXELS, replace=False))
+        idx = torch.from_numpy(pick).to(fr["output"].device)
+    arrays = {}
+    for name, t in (("output", fr["output"]), ("color", fr["color"]), ("resolved", renderer.resolved())):
+        px = t.reshape(P, -1)
+        arrays[name] = (px if idx is None else px.index_select(0, idx)).to(torch.float32).cpu().numpy()
+    ae = fr["auto_exposure"].cpu().numpy()
+    arrays["exposure"] = ae[:1].view(np.float32).copy()
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -309,8 +342,15 @@ def main():
                          "textures; rasterised by the HIP rasteriser); boxes = the round-1 analytic box atrium")
     ap.add_argument("--width", type=int, default=None, help="default 3840 (1920 for c2)")
     ap.add_argument("--height", type=int, default=None, help="default 2160 (1080 for c2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-frames", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the serial per-pass loop "
+                         "(ms_per_pass / ms_per_group, unfused groups), the roofline of the north-star kernels (with "
+                         "their in-frame pass events on during the timed steps) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed frame produced (framebuffer, HDR colour, "
+                         "resolved history, exposure) as DIR/<name>.npy, float32 (a seeded pixel sample of the images)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--profile-frames", type=int, default=20, help="--full: frames of the serial per-pass loop")
     ap.add_argument("--no-sky-lane", action="store_true", help="run CloudRendering on the frame stream too")
     ap.add_argument("--no-static-inputs", action="store_true",
                     help="fork the second lane at every frame start (no cross-frame overlap of the clouds)")
@@ -338,6 +378,8 @@ def main():
                     help="end-to-end frame: rasterise the scene mesh into the G-buffer and the 4096^2 sun shadow "
                          "map every frame (DepthPrepass / SunShadowDraw / GBufferGeneration in the graph)")
     args = ap.parse_args()
+    if args.metrics_jsonl and not args.full:
+        ap.error("--metrics-jsonl records the serial per-pass loop: it needs --full")
 
     rank, world, local_rank = multi_gpu.env()
     if world != args.gpus:
@@ -406,10 +448,11 @@ def main():
         probe_frames += 1
     torch.cuda.synchronize()
 
-    # HIP events around the north-star kernels on the launch stream, inside the timed region
+    # --full: HIP events around the north-star kernels on the launch stream, inside the timed region (the roofline's
+    # in-frame figures); a plain run times its frames without them
     comp = "Composition+GenerateLuminanceHistogram" if "Composition+GenerateLuminanceHistogram" in names else "Composition"
     timed = [names.index(comp), names.index("SSAOGeneration")]
-    probe_no_events = os.environ.get("SOC_BENCH_NO_PASS_EVENTS") == "1"   # diagnostic: frame time without them
+    probe_no_events = not args.full or os.environ.get("SOC_BENCH_NO_PASS_EVENTS") == "1"   # diagnostic: --full without them
     for i in timed:
         r.set_pass_timing(i, not probe_no_events)
     r.reset_timing()
@@ -443,6 +486,74 @@ def main():
     max_elapsed = multi_gpu.max_over_ranks(elapsed, device)
     ms_per_step = max_elapsed / args.steps * 1e3
     value = world * args.steps / max_elapsed
+    if args.dump_outputs:   # the last timed frame, before anything else renders into the frame's images
+        dump_outputs(args.dump_outputs, fr, r, rank)
+
+    # the renderer computes the bloom's last stage inside Composition in frames whose sky lane is the critical path
+    # (SOC_RENDERER_BLOOM_IN_COMPOSITION with a high-priority sky lane): the fourth bloom pass then launches nothing
+    bloom_in_comp = not args.no_bloom_in_composition and "BloomUpsample - 3+2" in names and r.side_queue() == 1
+    out = {
+        "metric": "frames/sec + ms/pass, Sponza 3840x2160 deferred+SSAO+TAA",
+        "value": round(value, 3),
+        "unit": "frames/sec",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32 (fp16/unorm8/d32 storage)",
+        "full": args.full,
+        "data": (f"synthetic: fBm terrain (seed 0x7E44) G-buffer + 4096^2 sun shadow map (scene_synth.c)" if terrain else
+                 f"synthetic: Sponza-proxy {'box atrium (scene_synth.c)' if sc is None else 'mesh (procedural atrium, ' + str(int(sc['mesh'].struct.triangle_count)) + ' triangles, the reference Sponza baseColor/normal textures (' + sc['texture_set'] + ')' + ('' if args.no_mips else ' with mip chains + 16x anisotropic sampling') + ', seed 0x5050)'}; "
+                 f"G-buffer + 4096^2 sun shadow map {'ray-cast on the host' if sc is None else 'rasterised once by the HIP rasteriser'}"),
+        "config": {"workload": f"{'Terrain' if terrain else 'Sponza-proxy'} {W}x{H} full screen-space chain "
+                               f"({args.config.upper()}): bloom x8, SSAO+blur, clouds, composition"
+                               f"{' with 128 point lights' if args.config == 'c3b' else ''}, auto-exposure, "
+                               f"TAA, AgX tone map",
+                   "resolution": [W, H], "f_sky": round(f_sky, 4), "parallelism": f"frame-per-gpu x{world}",
+                   "profile_frames": args.profile_frames if args.full else 0,
+                   "histogram_allreduce": exchange,
+                   "collective_backend": (dist.get_backend() if exchange else None),
+                   "sky_lane": ("CloudRendering + SkyCompose on a concurrent stream; " +
+                                ("the clouds of frame N+1 may start before frame N's TAA (static inputs)"
+                                 if not args.no_static_inputs else "forked at every frame start")),
+                   "sky_lane_queue": {1: "high priority", 2: "low priority", 0: "normal priority",
+                                      -1: "not chosen"}.get(r.side_queue(), "?"),
+                   "sky_lane_queue_choice": ("timed probe" if lane_q == "probe" else
+                                             f"fixed ({lane_q}: {'--sky-lane-queue' if args.sky_lane_queue != 'auto' else 'the configuration default'})"),
+                   "untimed_lane_probe_frames": probe_frames,
+                   "bloom_last_stage": ("inside Composition (mip1 -> [mip0] -> emissive term per tile in LDS; the "
+                                        "full-resolution bloom output is not written)" if bloom_in_comp
+                                        else "its own pass (writes the bloom output)"),
+                   "velocity_history": ("slot rotation (the G-buffer's velocity in the slot the next frame reads; "
+                                        "no copy)" if vslots else "copy fused into TAA"),
+                   "raster": (f"in-frame: DepthPrepass + SunShadowDraw (4096^2) + GBufferGeneration of the "
+                              f"{int(sc['mesh'].struct.triangle_count)}-triangle scene mesh") if args.raster
+                   else "off: G-buffer and shadow map are resident inputs"},
+        "ranks": per_rank,
+        "allreduce_us_per_frame": (round(sum(p["allreduce_us_per_frame"] for p in per_rank) / world, 2)
+                                   if exchange else None),
+    }
+
+    def write_frame():   # headless present: the RGBA8 framebuffer (PNG) or the HDR colour (EXR f16)
+        if args.write_frame.endswith(".exr"):
+            soc.write_exr(args.write_frame, soc.read_image(fr["color"]))
+        else:
+            soc.write_png(args.write_frame, soc.read_image(fr["output"]))
+
+    if not args.full:   # a plain run: the headline alone
+        if args.write_frame and rank == 0:
+            write_frame()
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            emit(json.dumps(out))
+            r.close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
 
     # ---- per-pass breakdown (separate, all passes evented, sky lane off so passes do not overlap) ----
     r.set_async(False)
@@ -459,16 +570,10 @@ def main():
     if args.metrics_jsonl and rank == 0:
         with open(args.metrics_jsonl, "w") as f:
             f.write("\n".join(metrics_lines) + "\n")
-    if args.write_frame and rank == 0:   # headless present: the RGBA8 framebuffer (PNG) or the HDR colour (EXR f16)
-        if args.write_frame.endswith(".exr"):
-            soc.write_exr(args.write_frame, soc.read_image(fr["color"]))
-        else:
-            soc.write_png(args.write_frame, soc.read_image(fr["output"]))
+    if args.write_frame and rank == 0:
+        write_frame()
     r.set_async(not args.no_sky_lane)
     stats = [st for st in stats if st[3]]     # passes with no work this frame (the folded fold pass) have no record
-    # the renderer computes the bloom's last stage inside Composition in frames whose sky lane is the critical path
-    # (SOC_RENDERER_BLOOM_IN_COMPOSITION with a high-priority sky lane): the fourth bloom pass then launches nothing
-    bloom_in_comp = not args.no_bloom_in_composition and "BloomUpsample - 3+2" in names and r.side_queue() == 1
     no_launch = {"BloomUpsample - 1+0"} if bloom_in_comp else set()
     ms_pass = {n: (None if n in no_launch else round(ms, 4)) for n, _, ms, _ in stats}
     ms_group_unfused = unfused_group_ms(fr, renderer_kw, g, args.profile_frames) if not args.raster else None
@@ -532,45 +637,7 @@ def main():
         dist.destroy_process_group()
         return
 
-    out = {
-        "metric": "frames/sec + ms/pass, Sponza 3840x2160 deferred+SSAO+TAA",
-        "value": round(value, 3),
-        "unit": "frames/sec",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32 (fp16/unorm8/d32 storage)",
-        "data": (f"synthetic: fBm terrain (seed 0x7E44) G-buffer + 4096^2 sun shadow map (scene_synth.c)" if terrain else
-                 f"synthetic: Sponza-proxy {'box atrium (scene_synth.c)' if sc is None else 'mesh (procedural atrium, ' + str(int(sc['mesh'].struct.triangle_count)) + ' triangles, the reference Sponza baseColor/normal textures (' + sc['texture_set'] + ')' + ('' if args.no_mips else ' with mip chains + 16x anisotropic sampling') + ', seed 0x5050)'}; "
-                 f"G-buffer + 4096^2 sun shadow map {'ray-cast on the host' if sc is None else 'rasterised once by the HIP rasteriser'}"),
-        "config": {"workload": f"{'Terrain' if terrain else 'Sponza-proxy'} {W}x{H} full screen-space chain "
-                               f"({args.config.upper()}): bloom x8, SSAO+blur, clouds, composition"
-                               f"{' with 128 point lights' if args.config == 'c3b' else ''}, auto-exposure, "
-                               f"TAA, AgX tone map",
-                   "resolution": [W, H], "f_sky": round(f_sky, 4), "parallelism": f"frame-per-gpu x{world}",
-                   "profile_frames": args.profile_frames,
-                   "histogram_allreduce": exchange,
-                   "collective_backend": (dist.get_backend() if exchange else None),
-                   "sky_lane": ("CloudRendering + SkyCompose on a concurrent stream; " +
-                                ("the clouds of frame N+1 may start before frame N's TAA (static inputs)"
-                                 if not args.no_static_inputs else "forked at every frame start")),
-                   "sky_lane_queue": {1: "high priority", 2: "low priority", 0: "normal priority",
-                                      -1: "not chosen"}.get(r.side_queue(), "?"),
-                   "sky_lane_queue_choice": ("timed probe" if lane_q == "probe" else
-                                             f"fixed ({lane_q}: {'--sky-lane-queue' if args.sky_lane_queue != 'auto' else 'the configuration default'})"),
-                   "untimed_lane_probe_frames": probe_frames,
-                   "bloom_last_stage": ("inside Composition (mip1 -> [mip0] -> emissive term per tile in LDS; the "
-                                        "full-resolution bloom output is not written)" if bloom_in_comp
-                                        else "its own pass (writes the bloom output)"),
-                   "velocity_history": ("slot rotation (the G-buffer's velocity in the slot the next frame reads; "
-                                        "no copy)" if vslots else "copy fused into TAA"),
-                   "raster": (f"in-frame: DepthPrepass + SunShadowDraw (4096^2) + GBufferGeneration of the "
-                              f"{int(sc['mesh'].struct.triangle_count)}-triangle scene mesh") if args.raster
-                   else "off: G-buffer and shadow map are resident inputs"},
+    out.update({
         # headline: the north-star pair (SURVEY.md §8d target: SSAO + deferred lighting >= 0.60 of HBM peak), each
         # kernel alone; the same kernels' in-frame figures beside them
         "roofline": {"kernels": ["SSAOGeneration", comp], "bound": "hbm", "achieved": round(pair_achieved, 1),
@@ -590,9 +657,6 @@ def main():
                          "CloudRendering": (clouds_roofline({"c3b": "c3"}.get(args.config, args.config) if args.scene == "mesh" or terrain else "", W, H,
                                                             ms_pass.get("CloudRendering", 0.0) * 1e3)
                                             if not args.raster else None)}},
-        "ranks": per_rank,
-        "allreduce_us_per_frame": (round(sum(p["allreduce_us_per_frame"] for p in per_rank) / world, 2)
-                                   if exchange else None),
         "ms_per_pass": ms_pass,
         # the reference's 12 GPU-metric groups (renderer.cpp:558-588) from the serial per-pass loop; a fused launch's time
         # is split between its groups in the ratio of the same passes unfused (ms_per_group_unfused: the reference's own
@@ -603,7 +667,7 @@ def main():
                                "Mapping by the unfused passes' time ratio"),
         "ms_per_group_unfused": ms_group_unfused,
         "gbs_per_pass": pass_gbs,
-    }
+    })
     if not args.no_cpu_baseline and world == 1:
         host_inputs = dict(gb)
         host_inputs["shadow"] = shadow

@@ -35,6 +35,48 @@ def test_ssao_bounds():
     assert bench.valu_bound("no_such_kernel", 1.0) is None
 
 
+def test_dump_outputs_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files; an image above the sample size is written as the same
+    seeded pixel sample in every run, a smaller one whole."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    class _Resolved:
+        def __init__(self, fr):
+            self.fr = fr
+
+        def resolved(self):
+            return self.fr["history_color"][1]
+
+    H, W = 37, 53
+    gen = torch.Generator().manual_seed(7)
+    fr = {"output": torch.randint(0, 256, (H, W, 4), dtype=torch.uint8, generator=gen),
+          "color": torch.rand((H, W, 4), generator=gen).to(torch.float16),
+          "history_color": [torch.zeros(H, W, 4, dtype=torch.float16),
+                            torch.rand((H, W, 4), generator=gen).to(torch.float16)],
+          "auto_exposure": torch.arange(257, dtype=torch.int32)}
+    fr["auto_exposure"][0] = int(np.array([0.75], np.float32).view(np.int32)[0])
+    bench.dump_outputs(str(tmp_path / "whole"), fr, _Resolved(fr))
+    d = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in ("output", "color", "resolved", "exposure")}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert np.array_equal(d["output"], fr["output"].reshape(-1, 4).numpy().astype(np.float32))
+    assert np.array_equal(d["color"], fr["color"].reshape(-1, 4).numpy().astype(np.float32))
+    assert np.array_equal(d["resolved"], fr["history_color"][1].reshape(-1, 4).numpy().astype(np.float32))
+    assert d["exposure"].dtype == np.float32 and d["exposure"].tolist() == [0.75]
+    # above the sample size: the same sorted, duplicate-free pixel sample twice
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 500)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), fr, _Resolved(fr), rank=0)
+    a, b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    assert a.shape == (500, 4) and np.array_equal(a, b)
+    pick = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(H * W, 500, replace=False))
+    assert len(np.unique(pick)) == 500
+    assert np.array_equal(a, d["output"][pick])
+    assert np.array_equal(np.load(tmp_path / "a" / "color.npy"), d["color"][pick])
+
+
 def test_cpu_baseline_per_pass_medians():
     """The CPU baseline: the oracle frame timed per frame and per pass (median after a warm-up)."""
     import bench

@@ -120,7 +120,7 @@ def test_c5_4k_exchange_vs_oracle(tmp_path, soc, oracle):
 def test_bench_exchange_rccl_world1():
     """bench.py --exchange at N = 1: the frames take PRE -> RCCL all-reduce (a world-size-1 group) -> POST and the line
     carries the backend and the all-reduce time per frame (SURVEY.md §8e's report)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--exchange", "--steps", "20", "--warmup", "5",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--exchange", "--steps", "20", "--warmup", "5",
            "--width", "640", "--height", "360", "--no-cpu-baseline", "--profile-frames", "2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
@@ -136,7 +136,7 @@ def test_bench_exchange_rccl_world1():
 
 
 def test_bench_gpus2_self_launch():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--width", "320", "--height", "180", "--no-cpu-baseline", "--profile-frames", "2"]
     p = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

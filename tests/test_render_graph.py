@@ -210,17 +210,33 @@ def test_ring_edges(soc):
                                          ("SkyCompose", "TemporalAntiAliasing+ToneMapping")}
 
 
-def test_ring_edges_raster_head(soc):
+def test_ring_edges_raster_head(soc, monkeypatch):
     """With a raster head the G-buffer pass rewrites depth every frame: it must follow the previous frame's
-    CloudRendering (second lane), which reads depth: the cross-lane WAR edge the end-of-call join used to cover."""
+    CloudRendering (second lane), which reads depth: the cross-lane WAR edge the end-of-call join used to cover.
+    The sun shadow draw joins the second lane only where its own workspace could be allocated (a device is present),
+    so the graph is checked with the draw pinned to the main lane (SOC_RENDERER_SHADOW_LANE=0, the graph of a machine
+    without a device) and, where the default puts it on the second lane, with the ring edge that placement adds."""
+    main_lane = {("SkyCompose", "ResolveLuminanceHistogram"), ("SkyCompose", "TemporalAntiAliasing+ToneMapping"),
+                 ("GBufferGeneration", "CloudRendering"), ("GBufferGeneration", "SkyCompose")}
+
+    def check(r, edges):
+        c = _carry(r)
+        assert "CloudRendering" in c["GBufferGeneration"]
+        assert {"SSAOGeneration", "TemporalAntiAliasing+ToneMapping"} <= c["GBufferGeneration"]
+        assert c["DepthPrepass"] == {"DepthPrepass", "GBufferGeneration"}   # WAW / WAR on the visibility buffer
+        assert _cross_lane_ring_edges(r) == edges
+
     r = _raster_renderer(soc)
-    c = _carry(r)
-    assert "CloudRendering" in c["GBufferGeneration"]
-    assert {"SSAOGeneration", "TemporalAntiAliasing+ToneMapping"} <= c["GBufferGeneration"]
-    assert c["DepthPrepass"] == {"DepthPrepass", "GBufferGeneration"}   # WAW / WAR on the visibility buffer
-    assert _cross_lane_ring_edges(r) == {("SkyCompose", "ResolveLuminanceHistogram"),
-                                         ("SkyCompose", "TemporalAntiAliasing+ToneMapping"),
-                                         ("GBufferGeneration", "CloudRendering"), ("GBufferGeneration", "SkyCompose")}
+    if r.pass_lane(r.pass_names().index("SunShadowDraw")) == 1:
+        # the shadow map is rewritten on the second lane after the previous frame's composition (main lane) read it
+        check(r, main_lane | {("SunShadowDraw", "Composition+GenerateLuminanceHistogram")})
+    else:
+        check(r, main_lane)
+    monkeypatch.setenv("SOC_RENDERER_SHADOW_LANE", "0")
+    soc.reload_tuning()
+    r = _raster_renderer(soc)
+    assert r.pass_lane(r.pass_names().index("SunShadowDraw")) == 0
+    check(r, main_lane)
 
 
 def test_ring_edges_without_sky_split(soc):

@@ -13,7 +13,9 @@ SAN = os.path.join(ROOT, "tools", "sanitize")
 def test_host_code_under_asan_ubsan(tmp_path):
     b = subprocess.run(["make", "-s", "-C", SAN, "-j8"], capture_output=True, text=True, timeout=600)
     assert b.returncode == 0, b.stdout + b.stderr
+    # lsan.supp: the ROCm runtime's own allocations on a machine with a device (stacks inside its libraries only)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0",
+               LSAN_OPTIONS=f"suppressions={os.path.join(SAN, 'lsan.supp')}:print_suppressions=0",
                UBSAN_OPTIONS="print_stacktrace=1", SAN_TMP=str(tmp_path))
     p = subprocess.run([os.path.join(SAN, "build", "san_host")], capture_output=True, text=True, timeout=600, env=env)
     out = p.stdout + p.stderr

@@ -34,7 +34,7 @@ if "--traffic" in sys.argv:
                               "hbm_bytes": int(round((2.0 * v["FETCH_SIZE"] + v["WRITE_SIZE"]) * 1024)),
                               "dispatches": v["dispatch_samples"]}
     meta = {"source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, --kernel-trace only) "
-                      "over `bench.py --steps 3 --warmup 1 --profile-frames 1`; per-dispatch means",
+                      "over `bench.py --full --steps 3 --warmup 1 --profile-frames 1`; per-dispatch means",
             "formula": "hbm_bytes = 2*FETCH_SIZE + WRITE_SIZE (KiB -> bytes; gfx950 FETCH_SIZE halving correction)",
             "resolution": [3840, 2160], "kernels": kernels,
             "scene": (sys.argv[sys.argv.index("--scene") + 1] if "--scene" in sys.argv else "mesh")}

@@ -1,7 +1,7 @@
 """Agreement of the bench line's roofline durations with rocprofv3. The bench measures the north-star kernels with HIP
 events on their stream twice: alone (the serial per-pass profile frames: the roofline's headline) and in its timed
 frames (lanes concurrent: `in_frame`). This takes a `tools/gpu.sh kt` kernel trace of the same command (`bench.py
---steps K --warmup W`: W warm-up frames, the untimed lane-probe frames, K timed frames, then the serial per-pass profile
+--full --steps K --warmup W`: W warm-up frames, the untimed lane-probe frames, K timed frames, then the serial per-pass profile
 frames) and averages each
 kernel over the same kind of launch: the profile frames for the headline, the timed frames for in_frame. The kernel
 trace's own `--stats` average mixes the three segments. A kernel trace changes how the two lanes overlap, so the
