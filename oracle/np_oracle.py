@@ -245,7 +245,10 @@ def ssao_generation(g, depth, normal, out_shape) -> np.ndarray:
     b = np.cross(t, n)
     radius, bias = float(g.ssao_radius), float(g.ssao_bias)
     occ = np.zeros(u.shape)
-    for i in range(int(g.ssao_kernel_size)):                                    # :195-210
+    # :195-210. kernelSamples has KERNEL_SIZE = 26 entries (:74-103) and the loop indexes it to ssao_kernel_size: past
+    # 26 the GLSL reads out of the constant array's bounds (undefined). The ABI's contract (SOC_SSAO_MAX_KERNEL) gives
+    # those taps no occlusion: the loop stops at 26, the divisor of :211 stays ssao_kernel_size.
+    for i in range(min(int(g.ssao_kernel_size), len(SSAO_KERNEL))):
         k = SSAO_KERNEL[i].astype(f64)
         s = frag + (t * k[0] + b * k[1] + n * k[2]) * radius
         off = apply(proj, np.concatenate([s, np.ones(u.shape)[..., None]], -1))
@@ -364,6 +367,9 @@ def luminance_bins(g, hdr) -> np.ndarray:
 
 
 def generate_luminance_histogram(g, hdr) -> np.ndarray:
+    # only invocations inside globals.resolution bin a texel, :65
+    rw, rh = int(g.resolution[0]), int(g.resolution[1])
+    hdr = np.asarray(hdr)[:max(rh, 0), :max(rw, 0)]
     return np.bincount(luminance_bins(g, hdr).ravel(), minlength=256).astype(np.uint64)
 
 
@@ -403,8 +409,8 @@ def agx_matrix(compression):
     return srgb_to_xyz @ np.linalg.inv(adjusted_to_xyz)
 
 
-def tone_mapping(g, color, exposure) -> np.ndarray:
-    """RGBA8_UNORM framebuffer of AgX_DS(color) (alpha 1)."""
+def tone_mapping(g, color, exposure, raw=False) -> np.ndarray:
+    """RGBA8_UNORM framebuffer of AgX_DS(color) (alpha 1); raw: the float64 values before the store."""
     c = np.asarray(color, f64)[..., :3]
     wc = np.maximum(c, 0.0) * 2.0 ** exposure
     M = agx_matrix(g.compression)
@@ -419,7 +425,7 @@ def tone_mapping(g, color, exposure) -> np.ndarray:
     wc = np.clip(wc, 0.0, 1.0)
     wc = wc @ np.linalg.inv(M).T
     out = np.concatenate([wc, np.ones(wc.shape[:-1] + (1,))], -1)
-    return to_unorm8(out)
+    return out if raw else to_unorm8(out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -433,11 +439,22 @@ LN2 = math.log(2.0)
 
 
 def _rsi(pos, d, radius):
-    pod = np.sum(pos * d, -1)
-    delta = pod * pod + radius * radius - np.sum(pos * pos, -1)
+    """rsi, :97-106, in fp32: the planet-scale squares (6.4e6^2 ~ 4e13, one fp32 ulp = 4e6) cancel in delta, so the
+    GLSL's own fp32 rounding moves the cloud march's start and end by metres and IS the result. In float64 the marched
+    positions differ from any fp32 evaluation by that much, and the steep cloud density (smoothstep(0.55, 0.6), 24 x 10
+    steps) turns it into tens of RGBA8 levels on single pixels away from the default sun (measured: 53 levels at a 3
+    degree sun, 12 with this function in fp32)."""
+    f = np.float32
+    pos, d, radius = np.asarray(pos).astype(f), np.asarray(d).astype(f), f(radius)
+
+    def dot(a, b):
+        return ((a[..., 0] * b[..., 0]).astype(f) + (a[..., 1] * b[..., 1]).astype(f) + (a[..., 2] * b[..., 2]).astype(f)).astype(f)
+
+    pod = dot(pos, d)
+    delta = (pod * pod + radius * radius - dot(pos, pos)).astype(f)
     ok = delta >= 0.0
-    sq = np.sqrt(np.where(ok, delta, 0.0))
-    return np.where(ok, -pod - sq, -1.0), np.where(ok, -pod + sq, -1.0)
+    sq = np.sqrt(np.where(ok, delta, f(0.0))).astype(f)
+    return np.where(ok, -pod - sq, f(-1.0)).astype(f64), np.where(ok, -pod + sq, f(-1.0)).astype(f64)
 
 
 def _bayer2(a):
@@ -465,7 +482,12 @@ def _noise3(noise, pos):
 
 
 def _clouds(noise, p, cam, elapsed):
-    h = np.linalg.norm(p + np.array([0.0, EARTH, 0.0]), axis=-1) - EARTH
+    # :236 in fp32 like _rsi: length(p + (0, 6371000, 0)) has an fp32 ulp of 0.5 m, so the GLSL's own rounding quantises
+    # the height the density is sampled at (measured with _rsi alone in fp32: 28 levels at a 3 degree sun, 9 with this)
+    f = np.float32
+    v = np.asarray(p).astype(f) + np.array([0.0, EARTH, 0.0], f)
+    sq = ((v[..., 0] * v[..., 0]).astype(f) + (v[..., 1] * v[..., 1]).astype(f) + (v[..., 2] * v[..., 2]).astype(f)).astype(f)
+    h = (np.sqrt(sq).astype(f) - f(EARTH)).astype(f64)
     q = np.stack([p[..., 0] + cam[0], h, p[..., 2] + cam[2]], -1)
     inside = (h >= CLOUD_MIN) & (h <= CLOUD_MAX)
     t = -1.0 * 0.02 * elapsed
@@ -581,8 +603,19 @@ def _volumetric_clouds(noise, d, sun, color, dither, cam, elapsed):
 
 
 def cloud_rendering(g, depth, noise) -> np.ndarray:
-    """RGBA8 clouds target (quirk Q6: full resolution; non-sky pixels (0.2, 0.4, 1.0))."""
-    H, W = depth.shape
+    """RGBA8 clouds target (quirk Q6: full resolution; non-sky pixels (0.2, 0.4, 1.0)). Pixels at or past
+    globals.resolution return before the store (:443) and stay 0."""
+    rw, rh = int(g.resolution[0]), int(g.resolution[1])
+    full = depth.shape
+    H, W = min(full[0], rh), min(full[1], rw)
+    if (H, W) != full:
+        out = np.zeros(full + (4,), np.uint8)
+        out[:H, :W] = _cloud_rendering(g, depth, noise, W, H)
+        return out
+    return _cloud_rendering(g, depth, noise, W, H)
+
+
+def _cloud_rendering(g, depth, noise, W, H) -> np.ndarray:
     rw, rh = int(g.resolution[0]), int(g.resolution[1])
     px, py = np.meshgrid(np.arange(W, dtype=f64), np.arange(H, dtype=f64))
     ru, rv = px / (rw - 1.0), py / (rh - 1.0)

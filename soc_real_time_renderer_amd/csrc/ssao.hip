@@ -258,7 +258,7 @@ struct SsaoPixel {
     bool skip;
     f3 frag;
     Aff ax, ay, aw, az, dzr;
-    float A1, B1;
+    float A1, dc;
 };
 
 // The per-pixel fetches of the setup: the normal sample, the random vector, and (SsaoDepth) the centre depth tap.
@@ -361,10 +361,14 @@ __device__ __forceinline__ SsaoPixel ssao_setup_from(float u, float v, const Ssa
     px.az = Aff{frag.z + p.bias, tr.z, br.z, nr.z};     // s.z + bias
     // SPARSE_IP range test in units of the radius (r > 0, host-checked): with vw = ip11 d + ip15, vz = ip10 d + ip14,
     // D1 = frag.z vw - vz = d A + B and D2 = s.z vw - vz = D1 + (s.z - frag.z) vw; r vw / |D1| = vw / |D1 / r| and
-    // sign(D2) = sign(D2 / r), so the tap needs vw, D1 / r (one fma each) and the per-pixel form (s.z - frag.z) / r
+    // sign(D2) = sign(D2 / r), so the tap needs vw, D1 / r and the per-pixel form (s.z - frag.z) / r.
+    // frag.z is the centre's vz / vw, so B = -dc A exactly and D1 = (d - dc) A: evaluated in that form (a subtraction
+    // and a product), because d A + B cancels to ulp(A): for a far or sky-edge pixel (|frag.z| of hundreds) and a small
+    // radius that is more than vw itself, and the range test and the occlusion sign of every tap become noise
+    // (radius 0.05 at 97 x 55).
     const float ir = p.inv_radius;
     px.A1 = (frag.z * ip[11] - ip[10]) * ir;
-    px.B1 = (frag.z * ip[15] - ip[14]) * ir;
+    px.dc = d;
     px.dzr = Aff{p.bias * ir, t.z, b.z, n.z};
     return px;
 }
@@ -401,7 +405,7 @@ __device__ __forceinline__ void ssao_pixel_px(int x, int y, const SsaoPixel& px,
     }
     const f3 frag = px.frag;
     const Aff ax = px.ax, ay = px.ay, aw = px.aw, az = px.az, dzr = px.dzr;
-    const float A1 = px.A1, B1 = px.B1;
+    const float A1 = px.A1, dc = px.dc;
     const float* ip = p.inv_proj.m;
     const float r = p.radius;
     const int W = depth.w, H = depth.h;
@@ -429,7 +433,7 @@ __device__ __forceinline__ void ssao_pixel_px(int x, int y, const SsaoPixel& px,
             const float btop = __builtin_fmaf(wx.y, b1 - b0, b0), bbot = __builtin_fmaf(wx.y, b3 - b2, b2);
             const f2v dd = {__builtin_fmaf(wy.x, abot - atop, atop), __builtin_fmaf(wy.y, bbot - btop, btop)};
             const f2v vw = pfma(bc2(ip[11]), dd, bc2(ip[15]));
-            const f2v d1 = pfma(dd, bc2(A1), bc2(B1));
+            const f2v d1 = (dd - bc2(dc)) * bc2(A1);
             const f2v q = vw * f2v{fast_rcp(fabsf(d1.x)), fast_rcp(fabsf(d1.y))};
             const f2v rc = {__builtin_amdgcn_fmed3f(q.x, 0.0f, 1.0f), __builtin_amdgcn_fmed3f(q.y, 0.0f, 1.0f)};
             const f2v range = rc * rc * pfma(bc2(-2.0f), rc, bc2(3.0f));   // smoothstep(0, 1, x)
@@ -443,16 +447,16 @@ __device__ __forceinline__ void ssao_pixel_px(int x, int y, const SsaoPixel& px,
         if (FULL || i < p.ksize) {
             const float kx = kKernel.v[i][0], ky = kKernel.v[i][1], kz = kKernel.v[i][2];
             const float rw = fast_rcp(aff(aw, kx, ky, kz));
-            float tx = 0.0f, ty = 0.0f;
+            float tx = 0.0f, ty = 0.0f, utx = 0.0f, uty = 0.0f;
             int fx, fy;
             if (SPARSE_IP) {   // 256 t + 0.5 directly, clamped to [0.5, 256 tmax + 0.5]; >= 0, so truncation floors
                 fx = (int)__builtin_amdgcn_fmed3f(__builtin_fmaf(aff(ax, kx, ky, kz), rw, cx0), 0.5f, tmax_x);
                 fy = (int)__builtin_amdgcn_fmed3f(__builtin_fmaf(aff(ay, kx, ky, kz), rw, cy0), 0.5f, tmax_y);
             } else {
-                tx = __builtin_fmaf(aff(ax, kx, ky, kz), rw, cx0);
-                ty = __builtin_fmaf(aff(ay, kx, ky, kz), rw, cy0);
-                tx = __builtin_amdgcn_fmed3f(tx, 0.0f, tmax_x);   // clamp: one v_med3, no NaN quieting
-                ty = __builtin_amdgcn_fmed3f(ty, 0.0f, tmax_y);
+                utx = __builtin_fmaf(aff(ax, kx, ky, kz), rw, cx0);
+                uty = __builtin_fmaf(aff(ay, kx, ky, kz), rw, cy0);
+                tx = __builtin_amdgcn_fmed3f(utx, 0.0f, tmax_x);   // clamp: one v_med3, no NaN quieting
+                ty = __builtin_amdgcn_fmed3f(uty, 0.0f, tmax_y);
                 // t >= 0, so truncation is the floor
                 fx = (int)__builtin_fmaf(tx, 256.0f, 0.5f);
                 fy = (int)__builtin_fmaf(ty, 256.0f, 0.5f);
@@ -467,7 +471,9 @@ __device__ __forceinline__ void ssao_pixel_px(int x, int y, const SsaoPixel& px,
             if (SPARSE_IP) {
                 vw = __builtin_fmaf(ip[11], dd, ip[15]);
             } else {
-                const float ex = (tx + 0.5f) * (2.0f / (float)W) - 1.0f, ey = (ty + 0.5f) * (2.0f / (float)H) - 1.0f;
+                // the reference unprojects the tap's own offset.xy (:205): only the texture read clamps to the image, so
+                // a tap that projects off screen keeps its unclamped ndc (the inverse projection's z / w rows read it)
+                const float ex = (utx + 0.5f) * (2.0f / (float)W) - 1.0f, ey = (uty + 0.5f) * (2.0f / (float)H) - 1.0f;
                 vz = ip[2] * ex + ip[6] * ey + ip[10] * dd + ip[14];
                 vw = ip[3] * ex + ip[7] * ey + ip[11] * dd + ip[15];
             }
@@ -475,7 +481,7 @@ __device__ __forceinline__ void ssao_pixel_px(int x, int y, const SsaoPixel& px,
                 // vw > 0 for every stored depth (the host selects this path only then), so with sd = vz / vw:
                 // r / |frag.z - sd| = r vw / |frag.z vw - vz| and sd >= s.z  <=>  s.z vw - vz <= 0 (one
                 // reciprocal per tap instead of two), both scaled by 1 / r (above)
-                const float d1 = __builtin_fmaf(dd, A1, B1);
+                const float d1 = (dd - dc) * A1;
                 const float rc = __builtin_amdgcn_fmed3f(vw * fast_rcp(fabsf(d1)), 0.0f, 1.0f);
                 const float range = rc * rc * __builtin_fmaf(-2.0f, rc, 3.0f);   // smoothstep(0, 1, x)
                 occ += (__builtin_fmaf(aff(dzr, kx, ky, kz), vw, d1) <= 0.0f) ? range : 0.0f;
@@ -697,7 +703,7 @@ __device__ __forceinline__ void ssao_consume_pair(const TapPair& t, const SsaoPi
     const float btop = __builtin_fmaf(wx.y, t.v[5] - t.v[4], t.v[4]), bbot = __builtin_fmaf(wx.y, t.v[7] - t.v[6], t.v[6]);
     const f2v dd = {__builtin_fmaf(wy.x, abot - atop, atop), __builtin_fmaf(wy.y, bbot - btop, btop)};
     const f2v vw = pfma(bc2(ip[11]), dd, bc2(ip[15]));
-    const f2v d1 = {__builtin_fmaf(dd.x, px.A1, px.B1), __builtin_fmaf(dd.y, px.A1, px.B1)};
+    const f2v d1 = (dd - bc2(px.dc)) * bc2(px.A1);
     // two scalar multiplies whose clamp is an output modifier (a packed multiply then two clamping v_max_f32 issue ~2.5x
     // the time: tools/microbench/valu_ops.hip); the same products
     const f2v rc = {__builtin_amdgcn_fmed3f(vw.x * fast_rcp(fabsf(d1.x)), 0.0f, 1.0f),
@@ -898,7 +904,12 @@ extern "C" int soc_ssao_generation(const soc_globals* g, soc_img depth, soc_img 
     else if (noise_table && sip) SOC_SSAO_LAUNCH(true, true, false);
     else if (noise_table) SOC_SSAO_LAUNCH(true, false, false);
     else if (sip && full) SOC_SSAO_LAUNCH(false, true, true);
-    else SOC_SSAO_LAUNCH(false, false, false);
+    else {
+        // a sparse inverse projection with a partial kernel and no table also lands here: the general kernel's taps
+        // are in texel space, not the sparse path's 1/256-texel steps
+        if (sip) fold_tap_constants(p, depth.width, depth.height, false);
+        SOC_SSAO_LAUNCH(false, false, false);
+    }
 #undef SOC_SSAO_LAUNCH
     return check_launch("ssao_generation");
 }

@@ -49,7 +49,9 @@ __global__ __launch_bounds__(kWorkgroup) void tonemap_generic(DImg src, DImg dst
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= dst.w || y >= dst.h) return;
     const float expo = exp2f(ae->exposure);
-    const f4 c = sample_h4(src, centre_uv(x, dst.w), centre_uv(y, dst.h));
+    // same extent: the pixel centre is the texel centre, so the texel itself (as tonemap_pair reads it). The bilinear
+    // form's zero-weight neighbour would turn an infinite neighbour into NaN (0 x inf) and the pixel black.
+    const f4 c = (src.w == dst.w && src.h == dst.h) ? fetch_h4(src, x, y) : sample_h4(src, centre_uv(x, dst.w), centre_uv(y, dst.h));
     store_px<FMT>(dst, x, y, agx(p, c, expo));
 }
 

@@ -143,10 +143,11 @@ def ao_footprint(diff_half, W, H):
 
 
 def frame_parity(soc, oracle, g, fr, hf, ae_ref, q, label, exposure_before, total_pixels=0, wide=False, check=True,
-                 masks=None):
+                 masks=None, ssao_step=SSAO_STEP):
     """Full-frame parity of one executed render-graph frame `fr` (device images, synchronised) against the oracle
     frame `hf` of the same inputs (oracle.frame already run; `ae_ref` its AutoExposure, `q` the history slot both wrote,
-    `exposure_before` the GPU's exposure before the frame). Records the achieved errors in PARITY_REPORTS and,
+    `exposure_before` the GPU's exposure before the frame, `ssao_step` the levels of one SSAO tap flip, 255 /
+    ssao_kernel_size). Records the achieved errors in PARITY_REPORTS and,
     with `check`, asserts the bounds above. Each downstream pass is also re-run on the oracle from the GPU's own
     inputs (the conditional check), so a pass's error is measured apart from what it inherits."""
     H, W = fr["depth"].shape
@@ -244,12 +245,12 @@ def frame_parity(soc, oracle, g, fr, hf, ae_ref, q, label, exposure_before, tota
     assert max(rep["tonemap_cond_levels"]) <= 1 and rep["tonemap_cond_levels"].get(0, 0) >= 0.999 * out.size, rep
     if "ssao_cond" in rep:
         sc_ = rep["ssao_cond"]
-        assert sc_["within2"] >= 0.995 and sc_["max"] <= 2 + SSAO_COND_FLIPS * SSAO_STEP, rep
+        assert sc_["within2"] >= 0.995 and sc_["max"] <= 2 + SSAO_COND_FLIPS * ssao_step, rep
     assert rep["ssao"]["within2"] >= 0.995 and rep["ssao"]["mean"] <= 0.5, rep
     # Q8: the GPU's random-vector table equals the oracle's bit for bit (both evaluate the hash with the same
     # deterministic sin / cos / pow), so the hard tap-flip bound holds on every pixel
     assert rep["ssao"].get("hash_differs", 0.0) == 0.0, rep
-    assert rep["ssao"]["max"] <= 2 + SSAO_FLIPS * SSAO_STEP, rep
+    assert rep["ssao"]["max"] <= 2 + SSAO_FLIPS * ssao_step, rep
     assert rep["clouds"]["within2"] >= 0.995, rep
     # the tail of the clouds differences is bounded too: the largest measured were 69 / 38 levels on two C4
     # pixels (a steep transmittance amplifying 1-ulp exp2 / sqrt differences), 16+ on 3e-5 of them
@@ -313,3 +314,284 @@ def mesh_inputs(W, H, **kw):
         _MESH_CACHE[key] = sponza_mesh_inputs(W, H, **kw)
     g, gb = _MESH_CACHE[key]
     return g, {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in gb.items()}
+
+
+# ------------------------------------------------------------------------------------------------ settings variants
+def _mat_set(field, m):
+    """4x4 float64 M[row, col] -> the ABI's glm column-major float[16]."""
+    field[:] = [float(v) for v in np.asarray(m, np.float64).T.reshape(16)]
+
+
+def _mat_get(field):
+    return np.array(list(field), np.float64).reshape(4, 4).T
+
+
+def set_projection(g, proj16):
+    """Replaces the camera projection (glm column-major float32[16]) and everything derived from it the way
+    soc_globals_frame_update derives it: the true inverse (soc_mat4_inverse), P * V and inv(P) * inv(V)."""
+    lib = soc.lib()
+    fp = C.POINTER(C.c_float)
+    P = (C.c_float * 16)(*[float(v) for v in proj16])
+    IP, PV, IPV = (C.c_float * 16)(), (C.c_float * 16)(), (C.c_float * 16)()
+    lib.soc_mat4_inverse(C.cast(IP, fp), C.cast(P, fp))
+    lib.soc_mat4_mul(C.cast(PV, fp), C.cast(P, fp), C.cast(g.camera_view_matrix, fp))
+    lib.soc_mat4_mul(C.cast(IPV, fp), C.cast(IP, fp), C.cast(g.camera_inverse_view_matrix, fp))
+    g.camera_projection_matrix[:] = list(P)
+    g.camera_inverse_projection_matrix[:] = list(IP)
+    g.camera_projection_view_matrix[:] = list(PV)
+    g.camera_inverse_projection_view_matrix[:] = list(IPV)
+
+
+ORTHO_HALF_HEIGHT, ORTHO_NEAR, ORTHO_FAR = 4.0, 0.1, 40.0
+
+
+def _projection_ortho(g):
+    """An orthographic camera (glm::orthoRH_NO, y flipped as Camera3D::resize flips the perspective): the inverse is
+    sparse with a constant w row (0, 0, 0, 1), the projection's w row is not the perspective's (0, 0, -1, 0)."""
+    W, H = int(g.resolution[0]), int(g.resolution[1])
+    hw = ORTHO_HALF_HEIGHT * W / H
+    P = (C.c_float * 16)()
+    soc.lib().soc_mat4_ortho_rh_no(C.cast(P, C.POINTER(C.c_float)), -hw, hw, -ORTHO_HALF_HEIGHT, ORTHO_HALF_HEIGHT,
+                                   ORTHO_NEAR, ORTHO_FAR)
+    P[5] *= -1.0
+    set_projection(g, P)
+
+
+def _projection_oblique(g):
+    """The frame's perspective with an oblique near plane: x and y coefficients in the clip-z row (the x, y and w rows,
+    so the rays through the eye, stay). The inverse's w row then depends on x and y (not sparse); w stays positive over
+    the frame: the coefficients move depth by <= 0.004 * 1.78 + 0.003 against the 0.2 of the w row's constant."""
+    P = list(g.camera_projection_matrix)
+    P[0 * 4 + 2] = 0.004     # column 0, row 2
+    P[1 * 4 + 2] = -0.003    # column 1, row 2
+    set_projection(g, P)
+
+
+def _sun_rotate_y(deg):
+    def f(g):
+        a = np.radians(deg)
+        x, y, z = (float(v) for v in g.sun_info.direction)
+        g.sun_info.direction[:] = [float(x * np.cos(a) + z * np.sin(a)), y, float(-x * np.sin(a) + z * np.cos(a))]
+    return f
+
+
+def _sun_elevation(deg, azimuth=0.7):
+    def f(g):
+        e = np.radians(deg)
+        d = -np.array([np.cos(e) * np.cos(azimuth), np.sin(e), np.cos(e) * np.sin(azimuth)])
+        g.sun_info.direction[:] = [float(v) for v in d]
+    return f
+
+
+def _resolution_scale(k):
+    def f(g):
+        g.resolution[0] = int(g.resolution[0]) * k
+        g.resolution[1] = int(g.resolution[1]) * k
+    return f
+
+
+def _resolution_shrink(g):
+    """A render resolution smaller than the image: the histogram bins only the top-left resolution[0] x resolution[1]."""
+    g.resolution[0] = int(g.resolution[0]) * 3 // 4
+    g.resolution[1] = int(g.resolution[1]) * 2 // 3
+
+
+# name -> {dotted soc.Globals field: value}; a key starting with "_" holds a function of g instead (matrices and vectors
+# derived from g's own). Every value the editor exposes (renderer.cpp:690-770) away from renderer.cpp:72-133's defaults.
+SETTINGS_VARIANTS = {
+    "default": {},
+    # SSAO
+    "ssao_k1": {"ssao_kernel_size": 1},
+    "ssao_k8": {"ssao_kernel_size": 8},
+    "ssao_k25": {"ssao_kernel_size": 25},
+    "ssao_k40": {"ssao_kernel_size": 40},      # the loop stops at the 26 kernel samples, the divisor is 40
+    "ssao_r005": {"ssao_radius": 0.05},
+    "ssao_r1": {"ssao_radius": 1.0},
+    "ssao_bias0": {"ssao_bias": 0.0},
+    "ssao_bias01": {"ssao_bias": 0.1},
+    "ssao_k8_r1_bias0": {"ssao_kernel_size": 8, "ssao_radius": 1.0, "ssao_bias": 0.0},
+    "ssao_ortho": {"_projection": _projection_ortho},
+    "ssao_ortho_k8": {"_projection": _projection_ortho, "ssao_kernel_size": 8},
+    "ssao_oblique": {"_projection": _projection_oblique},
+    "ssao_oblique_r1_bias01": {"_projection": _projection_oblique, "ssao_radius": 1.0, "ssao_bias": 0.1},
+    # composition
+    "df05": {"sun_info.darkening_factor": 0.5},
+    "df3": {"sun_info.darkening_factor": 3.0},
+    "ef20": {"sun_info.exponential_factor": -20.0},
+    "ef200": {"sun_info.exponential_factor": -200.0},
+    "aos04": {"ambient_occlussion_strength": 0.4},
+    "aos3": {"ambient_occlussion_strength": 3.0},
+    "ebs0": {"emissive_bloom_strength": 0.0},
+    "ebs5": {"emissive_bloom_strength": 5.0},
+    "ambient_rgb": {"ambient": (0.35, 0.05, 0.15)},
+    "sun_rot40": {"_sun": _sun_rotate_y(40.0)},
+    # tone map
+    "sat06": {"saturation": 0.6},
+    "sat14": {"saturation": 1.4},
+    "lin03": {"agxDs_linear_section": 0.3},
+    "peak08": {"peak": 0.8},
+    "comp005": {"compression": 0.05},
+    "comp03": {"compression": 0.3},
+    # auto exposure
+    "log_narrow": {"log_min_luminance": -2.0, "log_max_luminance": 2.0},
+    "log_wide": {"log_min_luminance": -20.0, "log_max_luminance": 20.0},
+    "res_clip": {"_resolution_clip": _resolution_shrink},
+    "speed0": {"adjustment_speed": 0.0},
+    "speed1e3": {"delta_time": 0.5, "adjustment_speed": 2000.0},      # delta_time x adjustment_speed = 1e3
+    "tl005": {"target_luminance": 0.05},
+    "tl1": {"target_luminance": 1.0},
+    # TAA
+    "fc0": {"frame_counter": 0},
+    "fc1": {"frame_counter": 1},
+    "res2x": {"_resolution_scale": _resolution_scale(2)},
+    # clouds
+    "sun_el3": {"_sun": _sun_elevation(3.0)},
+    "sun_el35": {"_sun": _sun_elevation(35.0)},
+    "sun_el80": {"_sun": _sun_elevation(80.0)},
+    "t0": {"elapsed_time": 0.0},
+    "t1234": {"elapsed_time": 1234.5},
+    # the render graph's middle frame: SSAO, composition, exposure and tone map changed at once
+    "all_at_once": {"ssao_kernel_size": 8, "ssao_radius": 0.6, "ssao_bias": 0.05,
+                    "sun_info.darkening_factor": 2.0, "sun_info.exponential_factor": -40.0,
+                    "ambient_occlussion_strength": 2.0, "emissive_bloom_strength": 3.5, "ambient": (0.2, 0.1, 0.3),
+                    "log_min_luminance": -8.0, "log_max_luminance": 6.0, "target_luminance": 0.4, "adjustment_speed": 4.0,
+                    "saturation": 1.3, "agxDs_linear_section": 0.25, "peak": 0.9, "compression": 0.25},
+}
+
+
+def apply_variant(g, name):
+    """Applies the named settings variant to a soc.Globals in place and returns it."""
+    for key, value in SETTINGS_VARIANTS[name].items():
+        if key.startswith("_"):
+            value(g)
+            continue
+        obj = g
+        *path, leaf = key.split(".")
+        for p in path:
+            obj = getattr(obj, p)
+        if isinstance(value, tuple):
+            getattr(obj, leaf)[:] = [float(v) for v in value]
+        else:
+            setattr(obj, leaf, value)
+    return g
+
+
+# The settings each pass reads; the "_" names are the variants' function keys. TAA takes the resolution larger than the
+# image, the histogram and the clouds the smaller one (their resolution guard).
+PASS_READS = {
+    "ssao": {"ssao_kernel_size", "ssao_radius", "ssao_bias", "_projection"},
+    "composition": {"sun_info.darkening_factor", "sun_info.exponential_factor", "ambient_occlussion_strength",
+                    "emissive_bloom_strength", "ambient", "_sun", "_projection"},
+    "exposure": {"log_min_luminance", "log_max_luminance", "_resolution_clip", "adjustment_speed", "delta_time",
+                 "target_luminance"},
+    "tonemap": {"saturation", "agxDs_linear_section", "peak", "compression"},
+    "taa": {"frame_counter", "_resolution_scale"},
+    "clouds": {"_sun", "elapsed_time", "_resolution_clip", "_projection"},
+}
+
+
+def variants_for(pass_name):
+    """The variants that change a setting `pass_name` reads, after "default"."""
+    reads = PASS_READS[pass_name]
+    return ["default"] + [n for n, v in SETTINGS_VARIANTS.items() if reads & set(v)]
+
+
+def ortho_heightfield(g, W, H):
+    """Depth and world-space normals of a stepped, rippled height field seen through g's orthographic camera (the ray
+    synthesiser shoots its rays through the eye, which an orthographic camera does not have): view depth 30 +- 4.5
+    inside the clip range, with 2-unit steps (occluders) every few view units. Returns (depth f32 (H, W), normal
+    RGBA16F (H, W, 4))."""
+    P, IP, IV = _mat_get(g.camera_projection_matrix), _mat_get(g.camera_inverse_projection_matrix), \
+        _mat_get(g.camera_inverse_view_matrix)
+    u, v = np.meshgrid((np.arange(W) + 0.5) / W, (np.arange(H) + 0.5) / H)
+    ndc = np.stack([u * 2 - 1, v * 2 - 1, np.zeros_like(u), np.ones_like(u)], -1)
+    vs = ndc @ IP.T
+    x, y = vs[..., 0] / vs[..., 3], vs[..., 1] / vs[..., 3]
+    step = 2.0 * (np.floor(x / 1.7 + 0.3 * y) % 2)
+    z = -(30.0 + 1.5 * np.sin(1.3 * x) * np.cos(0.9 * y) + step + 1.0 * np.sin(2.9 * y + 0.4 * x))
+    dzdx = -(1.5 * 1.3 * np.cos(1.3 * x) * np.cos(0.9 * y) + 0.4 * np.cos(2.9 * y + 0.4 * x))
+    dzdy = -(-1.5 * 0.9 * np.sin(1.3 * x) * np.sin(0.9 * y) + 2.9 * np.cos(2.9 * y + 0.4 * x))
+    nv = np.stack([-dzdx, -dzdy, np.ones_like(x)], -1)
+    nv /= np.linalg.norm(nv, axis=-1, keepdims=True)
+    clip = np.stack([x, y, z, np.ones_like(x)], -1) @ P.T
+    depth = (clip[..., 2] / clip[..., 3]).astype(np.float32)
+    assert (depth > 0.0).all() and (depth < 1.0).all()
+    # just inside unit length after the RGBA16F rounding: composition feeds the normal to acos(dot(h, n)) unnormalised
+    nw = nv @ IV[:3, :3].T * 0.998
+    normal = np.concatenate([nw, np.ones((H, W, 1))], -1).astype(np.float16)
+    return depth, normal
+
+
+def variant_inputs(name, W, H, **kw):
+    """sponza_inputs with the named variant applied. A variant that replaces the projection gets a G-buffer seen through
+    that projection: the ray-synthesised one for the oblique perspective, the height field's depth and normals for the
+    orthographic camera."""
+    g, gb = sponza_inputs(W, H, **kw)
+    apply_variant(g, name)
+    proj = SETTINGS_VARIANTS[name].get("_projection")
+    if proj is _projection_oblique:
+        shadow, noise = gb["shadow"], gb["noise"]
+        gb = scene.gbuffer(g, W, H)
+        gb["shadow"], gb["noise"] = shadow, noise
+    elif proj is _projection_ortho:
+        gb["depth"], gb["normal"] = ortho_heightfield(g, W, H)
+    return g, gb
+
+
+_VARIANT_INPUTS = {}
+
+
+def cached_variant_inputs(name, W, H, **kw):
+    """variant_inputs, computed once per (variant, extent, arguments) in a session and handed out as copies."""
+    key = (name, W, H, repr(sorted(kw.items())))
+    if key not in _VARIANT_INPUTS:
+        _VARIANT_INPUTS[key] = variant_inputs(name, W, H, **kw)
+    g, gb = _VARIANT_INPUTS[key]
+    return type(g).from_buffer_copy(bytes(g)), {k: v.copy() for k, v in gb.items()}
+
+
+def smooth_rgba16(H, W):
+    """A low-frequency RGBA16F image (colour gradient <= 0.2 per texel)."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    a = 1.5 + (np.sin(xx / 7.0) * np.cos(yy / 5.0))[..., None] * np.array([1.0, 0.8, 0.6, 0.4])
+    return a.astype(np.float16)
+
+
+def set_lights(g, points, spots):
+    """`points` point lights and `spots` spot lights in the atrium in front of SPONZA_CAMERA."""
+    g.point_light_count, g.spot_light_count = points, spots
+    for i in range(points):
+        L = g.point_lights[i]
+        L.position[:] = [-9.0 + 5 * i, 2.5, 0.7 - 0.5 * i]
+        L.color[:] = [1.0, 0.8, 0.6]
+        L.intensity = 3.0
+    for i in range(spots):
+        L = g.spot_lights[i]
+        L.position[:] = [-8.0 + 5 * i, 4.0, -1.0 + 1.5 * i]
+        L.direction[:] = [0.3, -1.0, 0.1 - 0.3 * i]
+        L.color[:] = [0.5, 0.7, 1.0]
+        L.intensity = 5.0
+        L.cut_off, L.outer_cut_off = 0.95, 0.85
+    return g
+
+
+def boundary_colours(g, n, rng):
+    """RGBA16F colours whose luminance maps within ~1e-3 of a bin boundary (the integers 1..255 of the
+    remap of generate_luminance_histogram.inl:64-69), half of them within the fast path's fallback margin:
+    the pixels where lum_bin_fast must hand over to the exact lum_bin."""
+    lmin, lmax = float(g.log_min_luminance), float(g.log_max_luminance)
+    out = []
+    while sum(len(o) for o in out) < n:
+        k = rng.integers(1, 256, 200_000)
+        t = (k - 1 + rng.uniform(-2e-3, 2e-3, k.size)) / 254.0       # target mapped - 1, over 254
+        lum = np.exp2(lmin + t * (lmax - lmin))
+        ok = (lum > 1.5e-3) & (lum < 6.0e4)
+        w = rng.dirichlet((1.0, 1.0, 1.0), k.size)[ok]               # random channel split of the luminance
+        lum = lum[ok]
+        rgb = w * (lum / (w @ np.array([0.2126, 0.7152, 0.0722])))[:, None]
+        rgb = rgb[(rgb < 6.0e4).all(axis=1)].astype(np.float16).astype(np.float64)
+        m = 1.0 + 254.0 * (np.log2(np.maximum(rgb @ np.array([0.2126, 0.7152, 0.0722]), 1e-30)) - lmin) / (lmax - lmin)
+        keep = np.abs(m - np.rint(m)) < 1e-3
+        out.append(rgb[keep])
+    rgb = np.concatenate(out)[:n]
+    return np.concatenate([rgb, np.ones((n, 1))], axis=1).astype(np.float16)
