@@ -285,7 +285,10 @@ int soc_ssao_blur(const soc_globals* g, soc_img ssao, soc_img target, soc_stream
  * `workspace` (optional, soc_cloud_rendering_workspace_size(target.width, target.height) bytes of
  * device memory) enables the compacted path: sky pixels are listed, and the cloud march is split at
  * its dense steps into (pixel, step) pairs so the sun-visibility marches are spread evenly over the
- * lanes; the result is bit-identical to the workspace-free single kernel. */
+ * lanes; the result is bit-identical to the workspace-free single kernel. The call is stateless: it builds its
+ * tables in the workspace (secondary-ray optical depths, noise quads) from this call's sun and noise on every call, and
+ * assumes nothing about what the workspace held before. A workspace given to a renderer (soc_frame_images) belongs to
+ * it between frames: see soc_renderer_invalidate_cloud_tables. */
 size_t soc_cloud_rendering_workspace_size(int32_t width, int32_t height);
 int soc_cloud_rendering(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
                         soc_stream stream);
@@ -460,6 +463,13 @@ int soc_renderer_set_current_history(soc_renderer* r, int32_t index);
  * stream of the current device, forked from `stream` at the start of the PRE phase and joined before
  * Composition, so it overlaps bloom and SSAO. Results are identical either way. */
 int soc_renderer_set_async(soc_renderer* r, int32_t enable);
+/* The renderer's CloudRendering keeps two static tables in images.clouds_workspace between frames: the secondary-ray
+ * optical-depth table, rebuilt when the bit pattern of dot(sun, sun) of the globals' sun direction changes, and the
+ * noise quad tables, rebuilt when the noise image's data pointer, format or pitch changes. A caller that rewrites the
+ * noise texels IN PLACE, or that uses the workspace for anything else between two frames (soc_cloud_rendering included),
+ * calls this before the next soc_renderer_execute: the next frame rebuilds both tables and clears the workspace's
+ * counter blocks. Host-side only (no launch, no synchronisation). */
+int soc_renderer_invalidate_cloud_tables(soc_renderer* r);
 /* The sky lane's hardware queue: 1 = a high-priority stream, 2 = low priority, 0 = normal priority (a queue HIP may
  * share with the caller's stream), -1 = not chosen yet (SOC_RENDERER_SKY_LANE_PROBE: after 16 frames, eight windows of
  * 32-128 frames alternate high / low priority as ABBA pairs; high is kept if it is faster by more than 2 % once their

@@ -534,6 +534,12 @@ class Renderer:
         results)."""
         _check(lib().soc_renderer_set_async(self.handle, int(bool(enable))), "soc_renderer_set_async")
 
+    def invalidate_cloud_tables(self) -> None:
+        """The static cloud tables in the frame's clouds workspace are rebuilt by the next frame
+        (soc_renderer_invalidate_cloud_tables): after rewriting the noise texels in place, or after using the
+        workspace outside the renderer."""
+        _check(lib().soc_renderer_invalidate_cloud_tables(self.handle), "soc_renderer_invalidate_cloud_tables")
+
     def current_history(self) -> int:
         return int(lib().soc_renderer_current_history(self.handle))
 

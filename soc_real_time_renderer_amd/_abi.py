@@ -232,6 +232,7 @@ FUNCTIONS = {
     "soc_renderer_current_history": (C.c_int32, [_P]),
     "soc_renderer_set_current_history": (C.c_int, [_P, C.c_int32]),
     "soc_renderer_set_async": (C.c_int, [_P, C.c_int32]),
+    "soc_renderer_invalidate_cloud_tables": (C.c_int, [_P]),
     "soc_scene_update": (_I, [C.POINTER(Globals), C.POINTER(Entity), C.c_int32, C.POINTER(C.c_float),
                               C.POINTER(C.c_float)]),
     "soc_renderer_add_pass": (_I, [_P, C.POINTER(PassDesc), PASS_CALLBACK, _P, C.c_char_p]),

@@ -685,6 +685,10 @@ struct soc_renderer {
     // first call are ordered before the second lane (that call's fork). Until then every second-lane pass waits for the
     // fork, as without the flag (the first call after create or a graph rebuild may follow the caller's input writes).
     bool inputs_ordered = false;
+    // CloudRendering's record of the clouds workspace between frames: which static tables it holds (and their keys) and
+    // the alternating counter blocks. Owned by the renderer (not a host-side cache keyed on the workspace pointer: a
+    // freed and reused allocation must not read as built).
+    soc::CloudState clouds_state;
 };
 
 namespace {
@@ -881,7 +885,7 @@ void build_passes_tail(soc_renderer* r) {
                  // as they run: high with these variants against low without)
                  const bool sky_bound = sky_lane_high(r) && tuning_knob("SOC_RENDERER_SKY_BOUND_VARIANTS", 1);
                  return soc::cloud_rendering_launch(g, r->img.depth, r->img.noise, r->img.clouds, r->img.clouds_workspace,
-                                                    (soc_stream)s, sky_bound);
+                                                    (soc_stream)s, sky_bound, &r->clouds_state);
              }, SOC_PASS_ASYNC);
     if (r->sky_split)
         add_pass(r, "SkyCompose", "Sky Rendering", pre, res_mask({SOC_RES_CLOUDS, SOC_RES_DEPTH}), sky_w,
@@ -1240,6 +1244,7 @@ static int ensure_side_lane(soc_renderer* r) {
     if (r->side && r->side_device == dev) return SOC_OK;
     if (r->side) {   // the caller moved to another device: rebuild the lane (and its events) there
         destroy_side_lane(r);
+        r->clouds_state.reset();   // the new lane is not ordered after the old one's clouds kernels
         for (auto& p : r->passes)
             if (p.done) { (void)hipEventDestroy(p.done); p.done = nullptr; p.done_recorded = false; }
     }
@@ -1645,7 +1650,19 @@ extern "C" int32_t soc_renderer_pass_lane(const soc_renderer* r, int32_t i) {
 
 extern "C" int soc_renderer_set_async(soc_renderer* r, int32_t enable) {
     if (!r) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_async: null renderer");
+    if (r->async != (enable != 0)) {
+        // the second-lane passes move to another stream: the first call after it forks them behind the caller's stream
+        // (SOC_RENDERER_STATIC_INPUTS would start CloudRendering ahead of the fork, beside the previous frame's clouds
+        // kernels on the other stream, which share its workspace)
+        r->inputs_ordered = false;
+    }
     r->async = enable != 0;
+    return SOC_OK;
+}
+
+extern "C" int soc_renderer_invalidate_cloud_tables(soc_renderer* r) {
+    if (!r) return set_error(SOC_E_INVALID_ARG, "soc_renderer_invalidate_cloud_tables: null renderer");
+    r->clouds_state.reset();   // the next CloudRendering rebuilds both tables and clears both counter blocks
     return SOC_OK;
 }
 

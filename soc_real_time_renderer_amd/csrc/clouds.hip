@@ -8,6 +8,7 @@
 // stage the 64x64 noise texture into LDS as packed 2x2 quads (one ds_read_b32 returns the four texels
 // of a bilinear REPEAT tap), 16 KiB per workgroup.
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "soc_internal.hpp"
@@ -905,9 +906,14 @@ constexpr int kClassifyTiles = 4;
 // graph selects it for a sky-bound frame (a high-priority sky lane) and the standalone pass by SOC_CLOUDS_CLASSIFY_HOIST.
 template <bool HOIST>
 __global__ __launch_bounds__(kWorkgroup) void clouds_classify(DImg depth, DImg target, CloudParams p, int vec_store,
-                                                       uint32_t* __restrict__ counter, uint32_t* __restrict__ list) {
+                                                       uint32_t* __restrict__ counter, uint32_t* __restrict__ list,
+                                                       uint32_t* __restrict__ zero_next) {
     __shared__ uint32_t wave_total[kClassifyTiles][4];
     __shared__ uint32_t wg_base;
+    // the NEXT frame's counter block (the alternating blocks of a renderer's workspace; null: none): the frame before
+    // this one used it last, and every kernel of that frame has completed in stream order. Every frame runs this
+    // kernel over the whole image, so a frame without sky clears it too.
+    if (zero_next && (blockIdx.x | blockIdx.y) == 0 && threadIdx.x < 64) zero_next[threadIdx.x] = 0u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x0 = blockIdx.x * 64 + (wave & 1) * 32 + (lane & 7) * 4;
     const int W = min(p.res_x, target.w), H = min(p.res_y, target.h);
@@ -1431,7 +1437,8 @@ namespace {
 // Workspace: counters (256 B: [0] sky pixels, [8..15] pair counts per shard) | sky list (u32) |
 // atmosphere (float4) | per-pixel dense mask (u32) | per-batch first pair (u32) | march geometry (2 float4) | pairs (u32) |
 // od per pair (float) | vis per pair (float) | od scratch of the density workgroups (24 x 256 float each, at most kDensityBlocks) |
-// the secondary-ray optical-depth table (kOdR x kOdM float2, 1 MiB).
+// the secondary-ray optical-depth table (kOdR x kOdM float2, 1 MiB) | sky-view table | noise tables |
+// the second counter block (256 B).
 // Pair capacity 2 per pixel of the image (8 shards).
 // Per 256-entry batch of the list: the physical index of its first pair (or kInline).
 // density workgroups the od scratch is sized for: the resident set (6 per CU on 256 CUs is 1536) times the largest grid
@@ -1447,6 +1454,7 @@ struct CloudWs {
     uint2* noise_wide;       // [kTableU2]
     uint32_t* noise_rows;    // [kRowU32]
     float4* sky_tab;  // sky-view table (kSvEntries x 2 float4)
+    uint32_t* counter_b;     // the second counter block (a renderer's frames alternate between the two)
     size_t bytes;
 };
 CloudWs cloud_ws_layout(void* base, size_t n) {
@@ -1487,6 +1495,8 @@ CloudWs cloud_ws_layout(void* base, size_t n) {
     off = al(off + (size_t)kTableU2 * 8);
     w.noise_rows = reinterpret_cast<uint32_t*>(b + off);
     off = al(off + (size_t)kRowU32 * 4);
+    w.counter_b = reinterpret_cast<uint32_t*>(b + off);
+    off += 256;
     w.bytes = off;
     return w;
 }
@@ -1502,8 +1512,23 @@ extern "C" int soc_cloud_rendering(const soc_globals* g, soc_img depth, soc_img 
     return soc::cloud_rendering_launch(g, depth, noise, target, workspace, stream, false);
 }
 
+namespace {
+int cloud_rendering_queue(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
+                          soc_stream stream, bool sky_bound, CloudState* state);
+}
 int soc::cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
-                                soc_stream stream, bool sky_bound) {
+                                soc_stream stream, bool sky_bound, CloudState* state) {
+    const int rc = cloud_rendering_queue(g, depth, noise, target, workspace, stream, sky_bound, state);
+    if (rc && state) {   // a frame that was not queued whole: the blocks are cleared anew, the tables rebuilt
+        state->blocks_primed = false;
+        state->invalidate_tables();
+    }
+    return rc;
+}
+
+namespace {
+int cloud_rendering_queue(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
+                          soc_stream stream, bool sky_bound, CloudState* state) {
     static const char* P = "soc_cloud_rendering";
     if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
     int rc = check_img(depth, SOC_FMT_D32F, P, "depth");
@@ -1543,12 +1568,21 @@ int soc::cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noi
     // the caller sized the workspace for the target extent (soc_cloud_rendering_workspace_size)
     CloudWs ws = cloud_ws_layout(workspace, (size_t)target.width * (size_t)target.height);
     ws.pb.store_geom = (uint32_t)tuning_knob("SOC_CLOUDS_GEOM", 1);
-    uint32_t* counter = ws.counter;
     uint32_t* list = ws.list;
-    // the frame's secondary-ray table (SOC_CLOUDS_OD_LUT=0: march every secondary ray, the single-lane kernel's bits);
-    // its kernel also clears the counter block, else a fill does
-    // The same kernel builds the frame's noise quad tables (SOC_CLOUDS_NOISE_TABLE=0: each march workgroup stages them
-    // from the noise image texel by texel, the same bytes).
+    // the secondary-ray table (SOC_CLOUDS_OD_LUT=0: march every secondary ray, the single-lane kernel's bits) and the
+    // noise quad tables (SOC_CLOUDS_NOISE_TABLE=0: each march workgroup stages them from the noise image texel by texel,
+    // the same bytes), both built by clouds_od_lut.
+    // Stateless (no `state`, soc_cloud_rendering; or SOC_CLOUDS_STATIC_TABLES=0): built on every call, by the kernel that
+    // also clears the call's counter block (block 0).
+    // A renderer's frames (`state`): both are static in real use (the od table depends only on C2 = dot(pSun, pSun), which
+    // changes when the sun is edited; the noise is an asset loaded once), so each is built when first needed and again
+    // only when its key changes (the bit pattern of C2; the noise image's data, format, pitch;
+    // soc_renderer_invalidate_cloud_tables for texels rewritten in place). The counter block then has no launch to clear
+    // it: frame N counts in block N & 1, and one workgroup of its clouds_classify clears block (N + 1) & 1, which frame
+    // N - 1 used last (all its kernels precede this frame's in stream order); both blocks are cleared when the renderer
+    // first uses the workspace this way. The classification runs over the whole image in every frame, so a frame
+    // without sky clears the next block too, and a sky frame after it starts from zero. (Not clouds_density: one more
+    // kernel argument took its scratch from 12 to 32 B per lane, +4.5 us at C3 and C4.)
     OdLut lut{nullptr, 0.0f};
     const bool use_lut = SOC_CLOUDS_PROFILE < 4 && tuning_knob("SOC_CLOUDS_OD_LUT", 1);
     const bool noise_tab = tuning_knob("SOC_CLOUDS_NOISE_TABLE", 1) != 0;
@@ -1557,10 +1591,62 @@ int soc::cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noi
     ws.pb.noise_quads = noise_tab ? ws.noise_quads : nullptr;
     ws.pb.noise_wide = noise_tab ? ws.noise_wide : nullptr;
     ws.pb.noise_rows = noise_tab ? ws.noise_rows : nullptr;
-    {
-        const int lut_blocks = use_lut ? ceil_div(kOdR * kOdM, kWorkgroup) : 1;
-        const int blocks_all = lut_blocks + (noise_tab ? ceil_div(kTableBuild, kWorkgroup) : 0);
-        float2* lt = use_lut ? ws.od_lut : nullptr;
+    // SOC_CLOUDS_STATIC_TABLES: 1 the static form, 0 the per-call build, default (-1) the static form except in a
+    // sky-bound frame above 1440p (the render graph's high-priority sky lane, as the atmosphere's position below): the
+    // C4 frame at 3840x2160 is 0.5 % slower without the 13 us build launch ahead of the classification (1498-1504 fps
+    // against 1506-1511 with it, five alternating runs: the lane's kernels start earlier, and clouds_sunvis then runs
+    // 12 us longer beside the main lane), while the sky-bound C2 frame at 1920x1080 gains 3 % and C3 1.5 %
+    // (profiles/r07_ab_static_tables.txt). The same bits in every form.
+    const int static_knob = tuning_knob("SOC_CLOUDS_STATIC_TABLES", -1);
+    const bool static_tables = static_knob >= 0 ? static_knob != 0 : !(sky_bound && (long long)W * H > 2560LL * 1440LL);
+    const bool cached = state && SOC_CLOUDS_PROFILE < 4 && static_tables;
+    uint32_t* counter = ws.counter;
+    uint32_t* zero_next = nullptr;
+    bool build_od = use_lut, build_noise = noise_tab;
+    if (cached) {
+        if (state->workspace != workspace) {   // another workspace: nothing of the record holds
+            state->invalidate_tables();
+            state->blocks_primed = false;
+            state->workspace = workspace;
+        }
+        if (!state->blocks_primed) {
+            if (hipMemsetAsync(ws.counter, 0, 256, s) != hipSuccess || hipMemsetAsync(ws.counter_b, 0, 256, s) != hipSuccess)
+                return set_error(SOC_E_HIP, "%s: counter block clear failed", P);
+            state->blocks_primed = true;
+        }
+        uint32_t c2_bits;
+        memcpy(&c2_bits, &C2, sizeof c2_bits);
+        if (state->od_valid && state->c2_bits != c2_bits) state->od_valid = false;
+        if (state->noise_valid && (state->noise_data != noise.data || state->noise_format != noise.format ||
+                                   state->noise_pitch != noise.pitch_bytes))
+            state->noise_valid = false;
+        build_od = use_lut && !state->od_valid;
+        build_noise = noise_tab && !state->noise_valid;
+        if (build_od) {
+            state->od_valid = true;
+            state->c2_bits = c2_bits;
+        }
+        if (build_noise) {
+            state->noise_valid = true;
+            state->noise_data = noise.data;
+            state->noise_format = noise.format;
+            state->noise_pitch = noise.pitch_bytes;
+        }
+        counter = (state->frame & 1u) ? ws.counter_b : ws.counter;
+        zero_next = (state->frame & 1u) ? ws.counter : ws.counter_b;
+        state->frame++;
+    } else if (state) {   // the per-call form leaves the blocks and the tables as any caller of the workspace would
+        state->invalidate_tables();
+        state->blocks_primed = false;
+        state->workspace = nullptr;
+    }
+    ws.pb.counts = counter + 8;
+    if (!cached || build_od || build_noise) {
+        // blocks [0, lut_blocks) build the od table (without it: one block, which only clears the counter block), the
+        // blocks after them the noise tables. The cached form's block is already clear; the kernel clears it again.
+        const int lut_blocks = build_od ? ceil_div(kOdR * kOdM, kWorkgroup) : 1;
+        const int blocks_all = lut_blocks + (build_noise ? ceil_div(kTableBuild, kWorkgroup) : 0);
+        float2* lt = build_od ? ws.od_lut : nullptr;
         if (noise.format == SOC_FMT_R8_UNORM)
             launch("clouds_od_lut", kWorkgroup, clouds_od_lut<true>, blocks_all, kWorkgroup, 0, s, lt, C2, counter, lut_blocks,
                    dimg(noise), ws.noise_quads, ws.noise_wide, ws.noise_rows);
@@ -1572,10 +1658,10 @@ int soc::cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noi
     const bool hoist = sky_bound || tuning_knob("SOC_CLOUDS_CLASSIFY_HOIST", 0);
     if (hoist)
         launch("clouds_classify", kWorkgroup, clouds_classify<true>, dim3(ceil_div(W, 64), ceil_div(H, 16 * kClassifyTiles)),
-               kWorkgroup, 0, s, dimg(depth), dimg(target), p, vec_store, counter, list);
+               kWorkgroup, 0, s, dimg(depth), dimg(target), p, vec_store, counter, list, zero_next);
     else
         launch("clouds_classify", kWorkgroup, clouds_classify<false>, dim3(ceil_div(W, 64), ceil_div(H, 16 * kClassifyTiles)),
-               kWorkgroup, 0, s, dimg(depth), dimg(target), p, vec_store, counter, list);
+               kWorkgroup, 0, s, dimg(depth), dimg(target), p, vec_store, counter, list, zero_next);
     // One resident wave set per kernel, grid-stride over the list / pairs: the long per-item work is
     // balanced over all SIMDs instead of running as a second, partially filled round.
     static int res_atmos = 0, res_density = 0, res_sunvis = 0, res_sunvis_n = 0, res_sunvis_r = 0, res_resolve = 0;
@@ -1708,3 +1794,4 @@ int soc::cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noi
     }
     return check_launch("cloud_rendering");
 }
+}  // namespace

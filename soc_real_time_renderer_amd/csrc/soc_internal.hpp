@@ -100,8 +100,23 @@ bool composition_pair_applicable(const soc_globals* g, const soc_img& target, co
 // soc_cloud_rendering; sky_bound (the render graph's sky lane runs at high priority): the variants that are faster
 // only where the sky lane is the frame's critical path (the density grid at twice the resident set, the classification's
 // hoisted depth samples). The same bits either way.
+// `state` (the render graph's CloudRendering; null: the stateless entry, which builds every table and clears its
+// counter block on every call): the renderer-owned record of what the workspace holds between frames.
+struct CloudState {
+    // static tables (SOC_CLOUDS_STATIC_TABLES, default 1): built when first needed and when their key changes
+    bool od_valid = false, noise_valid = false;
+    uint32_t c2_bits = 0;                 // od table: the bit pattern of dot(pSun, pSun)
+    const void* noise_data = nullptr;     // noise tables: the noise image's (data, format, pitch)
+    int32_t noise_format = 0, noise_pitch = 0;
+    void* workspace = nullptr;            // the workspace the tables and counter blocks were built in
+    // two counter blocks, alternating by frame: frame N uses block N & 1 and its clouds_classify clears the other
+    bool blocks_primed = false;           // both blocks were cleared and every frame since ran the alternating form
+    uint32_t frame = 0;
+    void invalidate_tables() { od_valid = noise_valid = false; }
+    void reset() { *this = CloudState(); }
+};
 int cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
-                           soc_stream stream, bool sky_bound);
+                           soc_stream stream, bool sky_bound, CloudState* state = nullptr);
 int sky_compose_launch(const soc_globals* g, soc_img target, soc_img depth, soc_img clouds, uint32_t* scratch,
                        soc_stream stream);
 int histogram_fold_launch(uint32_t* scratch, soc_auto_exposure* ae, soc_stream stream);
