@@ -212,12 +212,20 @@ __device__ __forceinline__ void down21_vpair(const uint2 (*t)[TW], int c0, int r
 // the tile loads' latency hides behind the filter instead of being waited on (the one-tile kernel waits on its
 // loads and barriers for 61 % of its wave cycles, profiles/r03_sq_stalls.json: 47.5 -> 42.9 us serial at 4K). The
 // same arithmetic and bits as that one-tile-per-workgroup kernel.
-template <int MODE>
+// ZS (tuning knob SOC_BLOOM_ZERO_SKIP, default 1): a tile whose whole clamped emissive footprint (EW x EH, as loaded) has
+// the bit pattern 0x0000 in every RGB half skips both filters and two of the three barriers and stores
+// pack3(+0, +0, +0): every sum starts at +0 and adds fma(+0, w, acc) with w > 0, so those are the bits the filters give
+// (-0, NaN, Inf and subnormals are other bit patterns and take the filters). Each wave ORs its lanes' texels (in
+// registers for the et store) and leaves its vote in LDS before the barrier that follows that store, so the filtered
+// path keeps its three barriers and its order (tests/test_gpu_bloom_zero_skip.py).
+template <int MODE, bool ZS>
 __global__ __launch_bounds__(kWorkgroup) void bloomw_down01p(DImg E, DImg M1, int ntx, int nty) {
     constexpr int W1_OW = W1<MODE>::OW, W1_OH = W1<MODE>::OH, W1_MW = W1<MODE>::MW, W1_MH = W1<MODE>::MH,
                   W1_EW = W1<MODE>::EW, W1_EH = W1<MODE>::EH, RUN = W1<MODE>::RUN;
+    static_assert(kWorkgroup == 256, "four waves: one vote word each");
     __shared__ uint2 et[W1_EH][W1_EW];
     __shared__ uint2 mt[W1_MH][W1_MW];
+    __shared__ uint4 zv[2];   // [slot]: the four waves' votes (non-zero = a non-zero RGB half), slots alternate per tile
     constexpr int NT = W1_EW * W1_EH, KR = (NT + 255) / 256;
     const int tid = threadIdx.x, n = ntx * nty, G = (int)gridDim.x;
     int er[KR], ec[KR];
@@ -244,16 +252,52 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_down01p(DImg E, DImg M1, in
             if (tid + 256 * k < NT)
                 v[k] = row_ptr<uint2>(E, clampi(ey0 + er[k], 0, E.h - 1))[clampi(ex0 + ec[k], 0, E.w - 1)];
     };
+    // the wave's vote on the texels in v, left in zv[slot]; voted(): after a barrier, whether the workgroup saw only zeros
+    auto vote = [&](int slot) {
+        uint32_t nz = 0u;
+#pragma unroll
+        for (int k = 0; k < KR; ++k)
+            if (tid + 256 * k < NT) nz |= v[k].x | (v[k].y & 0xffffu);   // alpha (v.y's high half) plays no part
+        const bool any = __ballot(nz != 0u) != 0ull;
+        if ((tid & 63) == 0) reinterpret_cast<uint32_t*>(&zv[slot])[tid >> 6] = any ? 1u : 0u;
+    };
+    auto voted = [&](int slot) {
+        const uint4 z = zv[slot];
+        return __builtin_amdgcn_readfirstlane((int)(z.x | z.y | z.z | z.w)) == 0;
+    };
     int t = (int)blockIdx.x;
+    int slot = 0;
+    const uint2 zpx = pack3(C3{0.0f, 0.0f, 0.0f});
     if (t < n) fetch(t);
     for (; t < n; t += G) {
 #pragma unroll
         for (int k = 0; k < KR; ++k)
             if (tid + 256 * k < NT) et[er[k]][ec[k]] = v[k];
+        if constexpr (ZS) vote(slot);   // rides on the barrier the tile needs anyway
         __syncthreads();
         if (t + G < n) fetch(t + G);   // in flight while this tile is filtered
         int X0, Y0;
         tile_origin(t, X0, Y0);
+        if constexpr (ZS) {
+            const bool zero = voted(slot);   // workgroup-uniform
+            slot ^= 1;
+            if (zero) {
+                // nothing of this tile is read from et / mt, so the next tile may overwrite them without a barrier
+                if constexpr (MODE == 2) {
+                    if (tid < W1_OW * W1_OH / 2) {
+                        const int q = tid / W1_OW, ox = tid - q * W1_OW;
+                        const int X = X0 + ox, Y = Y0 + 2 * q;
+                        if (X < M1.w && Y < M1.h) row_ptr_w<uint2>(M1, Y)[X] = zpx;
+                        if (X < M1.w && Y + 1 < M1.h) row_ptr_w<uint2>(M1, Y + 1)[X] = zpx;
+                    }
+                } else {
+                    const int oy = tid / W1_OW, ox = tid - oy * W1_OW;
+                    const int X = X0 + ox, Y = Y0 + oy;
+                    if (oy < W1_OH && X < M1.w && Y < M1.h) row_ptr_w<uint2>(M1, Y)[X] = zpx;
+                }
+                continue;
+            }
+        }
         const int mx0 = 2 * X0 - 2, my0 = 2 * Y0 - 2, ex0 = mx0 - 2, ey0 = my0 - 2;
         // register-blocked runs unless the tile's mip0 rows reach past the image's top or bottom (there a clamped row
         // repeats, which the fixed row stride does not follow): a uniform branch
@@ -574,18 +618,23 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_up10(DImg S1, DImg O, bool 
 // horizontal pass into an fp32 LDS tile and a vertical pass: per mip0 entry 4 + 4 taps instead of 16, per output 3 + 3
 // instead of 9. The same weights and footprints (the mip0 entries still rounded to RGBA16F, as the chain stores them);
 // the sums are grouped by rows, so the last fp32 bits may differ from bloomw_up10 (within the RGBA16F tolerance).
-__global__ __launch_bounds__(kWorkgroup) void bloomw_up10s(DImg S1, DImg O, bool vec, int swz) {
+__global__ __launch_bounds__(kWorkgroup) void bloomw_up10s(DImg S1, DImg O, bool vec, int swz, bool zs) {
     __shared__ Up10Tile<U_OW, U_OH> t;   // bloom_w.hpp (shared with Composition's in-kernel upsample)
     const int tid = threadIdx.x;
     int tbx, tby;
     xcd_order(swz, tbx, tby);
     const int X0 = tbx * U_OW, Y0 = tby * U_OH;
-    t.build(S1, X0, Y0, O.w, O.h, tid);
+    const bool zero = t.build(S1, X0, Y0, O.w, O.h, tid, zs);   // zs: SOC_BLOOM_ZERO_SKIP (an all-zero mip1 tile)
+    const uint2 zpx = pack3(C3{0.0f, 0.0f, 0.0f});
     // 1:1 vertical and the stores (pairs)
     for (int i = tid; i < (U_OW / 2) * U_OH; i += 256) {
         const int r = i / (U_OW / 2), pc = i - r * (U_OW / 2);
         const int x = X0 + 2 * pc, y = Y0 + r;
         if (x >= O.w || y >= O.h) continue;
+        if (zero) {
+            store2(O, x, y, zpx, zpx, vec);
+            continue;
+        }
         C3 o[2];
         t.out(r, 2 * pc, o);
         store2(O, x, y, pack3(o[0]), pack3(o[1]), vec);
@@ -609,6 +658,11 @@ __device__ __forceinline__ uint32_t up_from_left(uint32_t v) {   // lane i <- la
 __device__ __forceinline__ uint32_t up_from_right(uint32_t v) {  // lane i <- lane i+1 (wave_shl:1)
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, false);
 }
+// ZS (SOC_BLOOM_ZERO_SKIP, default 1): while every RGB half of every mip1 tap the wave has loaded is 0x0000, every row sum
+// is +0 in every lane (sums of fma(+0, w > 0, +0), the DPP neighbours included), so the strip's leading output rows
+// skip the 1:2 sums, the shifts and the combine and store pack3(+0, +0, +0): the same bits. The mip1 loads stay: they
+// are the evidence.
+template <bool ZS>
 __global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int nwx, int nwaves) {
     const int lane = (int)(threadIdx.x & 63);
     const int wid = (int)blockIdx.x * (kWorkgroup / 64) + (int)(threadIdx.x >> 6);
@@ -638,14 +692,20 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int 
         for (int k = 0; k < 4; ++k) madd(a, t[k], wk[k]);
         return a;
     };
+    // the RGB halves' bit patterns of one mip1 row's taps, ORed (alpha plays no part)
+    auto rgb_or = [&](const uint2 (&t)[4]) {
+        return t[0].x | t[1].x | t[2].x | t[3].x | ((t[0].y | t[1].y | t[2].y | t[3].y) & 0xffffu);
+    };
     // ring[i]: the sum of mip1 row base + i; pend: the taps of row base + 5
     C3 ring[5];
     uint2 pend[4];
+    uint32_t nz = 0u;
     int base = (max(Y0 - 1, 0) >> 1) - 2;
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         taps(base + i, pend);
         ring[i] = h12(pend);
+        if constexpr (ZS) nz |= rgb_or(pend);
     }
     taps(base + 5, pend);
     // this lane's mip0 texel of row cy (the second pass, rounded to RGBA16F), then the row's 1:1 horizontal sum
@@ -676,9 +736,32 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int 
         madd(hs, r, 1.0f);
         return hs;
     };
-    C3 hq0 = hrow(max(Y0 - 1, 0)), hq1 = hrow(min(Y0, H0 - 1));
     const bool out_lane = lane >= 1 && lane <= R_OW && x < W0;
-    for (int y = Y0; y < min(Y0 + R_TH, H0); ++y) {
+    int y0 = Y0;   // the first output row still to be computed
+    if constexpr (ZS) {
+        // while every mip1 row met so far is zero across the wave (one ballot per new row), ring[] and every row sum are
+        // +0: the ring only moves its base, and the output rows are the constant. The strip's mip0 rows in order: s = 0, 1
+        // are the rows above and at output row Y0, s = k + 2 the row below output row Y0 + k. The first non-zero row
+        // ends this for the rest of the strip: the dense rows below pay one ballot per strip, not one per row.
+        if (__ballot(nz != 0u) == 0ull) {
+            const uint2 zpx = pack3(C3{0.0f, 0.0f, 0.0f});
+            const int ns = min(Y0 + R_TH, H0) - Y0 + 2;
+            int s = 0;
+            for (; s < ns; ++s) {
+                const int jb = (clampi(Y0 - 1 + s, 0, H0 - 1) >> 1) - 2;
+                if (jb > base) {
+                    if (__ballot(rgb_or(pend) != 0u) != 0ull) break;   // hrow() below takes this row into the ring
+                    base = jb;
+                    taps(base + 5, pend);
+                }
+                if (s >= 2 && out_lane) row_ptr_w<uint2>(O, Y0 + s - 2)[x] = zpx;
+            }
+            // rows y0 - 1 and y0 are +0 like the whole ring: hrow() recomputes them from it (whichever entries it takes)
+            y0 = Y0 + max(s - 2, 0);
+        }
+    }
+    C3 hq0 = hrow(max(y0 - 1, 0)), hq1 = hrow(min(y0, H0 - 1));
+    for (int y = y0; y < min(Y0 + R_TH, H0); ++y) {
         const C3 hq2 = hrow(min(y + 1, H0 - 1));
         C3 o;
         o.r = __builtin_fmaf(hq2.r, 1.0f / 16.0f, __builtin_fmaf(hq1.r, 2.0f / 16.0f, hq0.r * (1.0f / 16.0f)));
@@ -692,7 +775,7 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int 
 
 // Workgroups of 256 lanes of bloomw_down01p resident on the whole device at once (the persistent kernel's grid bound),
 // queried once per device and cached (the occupancy query is not on the per-frame enqueue path).
-template <int MODE>
+template <int MODE, bool ZS>
 int down01p_resident_set() {
     constexpr int kMaxDevices = 64;
     static int cached[kMaxDevices] = {};
@@ -700,7 +783,7 @@ int down01p_resident_set() {
     (void)hipGetDevice(&dev);
     if (dev >= 0 && dev < kMaxDevices && cached[dev]) return cached[dev];
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, bloomw_down01p<MODE>, 256, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, bloomw_down01p<MODE, ZS>, 256, 0);
     const int n = std::max(per, 1) * cus;
     if (dev >= 0 && dev < kMaxDevices) cached[dev] = n;
     return n;
@@ -713,18 +796,25 @@ bool a16(const soc_img& im) { return im.pitch_bytes % 16 == 0 && reinterpret_cas
 int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage) {
     const DImg E = dimg(emissive), M1 = dimg(mips[1]), M3 = dimg(mips[3]), O = dimg(output);
     const int swz = 1;   // XCD-aware order: halo re-reads served by L2 (2.0x -> 1.0x HBM traffic)
+    // all-zero tiles / rows skip their filters (bloomw_down01p, bloomw_up10r): 0 = every tile filtered, the same bits
+    const bool zero_skip = tuning_knob("SOC_BLOOM_ZERO_SKIP", 1) != 0;
     if (stage == 0 || stage == 1) {
         // persistent: one resident set of workgroups (a multiple of 8, so a workgroup's tiles stay on its XCD)
-        auto w1 = [&](auto mode) {
+        auto w1 = [&](auto mode, auto zs) {
             constexpr int R = decltype(mode)::value;
+            constexpr bool Z = decltype(zs)::value;
             const int ntx = ceil_div(mips[1].width, W1<R>::OW), nty = ceil_div(mips[1].height, W1<R>::OH);
-            const int grid = std::max(8, (std::min(ntx * nty, down01p_resident_set<R>()) / 8) * 8);
-            launch("bloomw_down01p", kWorkgroup, bloomw_down01p<R>, grid, kWorkgroup, 0, s, E, M1, ntx, nty);
+            const int grid = std::max(8, (std::min(ntx * nty, down01p_resident_set<R, Z>()) / 8) * 8);
+            launch("bloomw_down01p", kWorkgroup, bloomw_down01p<R, Z>, grid, kWorkgroup, 0, s, E, M1, ntx, nty);
+        };
+        auto w1z = [&](auto mode) {
+            if (zero_skip) w1(mode, std::true_type{});
+            else w1(mode, std::false_type{});
         };
         const int mode = tuning_knob("SOC_BLOOM_W1_REG", 1);
-        if (mode == 2) w1(std::integral_constant<int, 2>{});
-        else if (mode == 1) w1(std::integral_constant<int, 1>{});
-        else w1(std::integral_constant<int, 0>{});
+        if (mode == 2) w1z(std::integral_constant<int, 2>{});
+        else if (mode == 1) w1z(std::integral_constant<int, 1>{});
+        else w1z(std::integral_constant<int, 0>{});
     }
     if (stage == 0 || stage == 2) {
         dim3 g(ceil_div(mips[3].width, W2_OW), ceil_div(mips[3].height, W2_OH));
@@ -747,9 +837,12 @@ int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const so
         dim3 g(ceil_div(output.width, U_OW), ceil_div(output.height, U_OH));
         if (tuning_knob("SOC_BLOOM_UP10_REG", 1)) {
             const int nwx = ceil_div(output.width, R_OW), nwaves = nwx * ceil_div(output.height, R_TH);
-            launch("bloomw_up10r", kWorkgroup, bloomw_up10r, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves);
+            if (zero_skip)
+                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<true>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves);
+            else
+                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<false>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves);
         } else if (tuning_knob("SOC_BLOOM_UP_SEP", 1))
-            launch("bloomw_up10s", kWorkgroup, bloomw_up10s, g, kWorkgroup, 0, s, M1, O, a16(output), swz);
+            launch("bloomw_up10s", kWorkgroup, bloomw_up10s, g, kWorkgroup, 0, s, M1, O, a16(output), swz, zero_skip);
         else
             launch("bloomw_up10", kWorkgroup, bloomw_up10, g, kWorkgroup, 0, s, M1, O, a16(output), swz);
     }

@@ -25,13 +25,15 @@ __device__ __forceinline__ uint2 pack3(const C3& c) { return pack_h4(f4{c.r, c.g
 
 // Clamp-to-edge tile load: t[r][c] = im[clamp(oy + r)][clamp(ox + c)]. Each lane issues its loads four at a time
 // before their LDS stores (one memory latency per four rounds of the 256-lane loop instead of one per round).
+// Returns the OR of the RGB halves' bit patterns of the texels this lane loaded (0: all +0; alpha left out).
 template <int TW, int TH>
-__device__ __forceinline__ void load_tile(const DImg& im, int ox, int oy, uint2 (*t)[TW], int tid) {
+__device__ __forceinline__ uint32_t load_tile(const DImg& im, int ox, int oy, uint2 (*t)[TW], int tid) {
     constexpr int N = TW * TH;
     auto at = [&](int i) {
         const int r = i / TW, c = i - r * TW;
         return row_ptr<uint2>(im, clampi(oy + r, 0, im.h - 1)) + clampi(ox + c, 0, im.w - 1);
     };
+    uint32_t nz = 0u;
     for (int i0 = tid; i0 < N; i0 += 4 * 256) {
         const int i1 = i0 + 256, i2 = i1 + 256, i3 = i2 + 256;
         const uint2 a = *at(i0);
@@ -43,7 +45,9 @@ __device__ __forceinline__ void load_tile(const DImg& im, int ox, int oy, uint2 
         if (i1 < N) t[i1 / TW][i1 % TW] = b;
         if (i2 < N) t[i2 / TW][i2 % TW] = c;
         if (i3 < N) t[i3 / TW][i3 % TW] = d;
+        nz |= a.x | b.x | c.x | d.x | ((a.y | b.y | c.y | d.y) & 0xffffu);
     }
+    return nz;
 }
 
 // up 1:2 weights: k = 0..3 along the 4-texel footprint
@@ -69,13 +73,22 @@ struct Up10Tile {
         uint2 mt[MH][MW];
     };
     float hr[HR][MW], hg[HR][MW], hb[HR][MW];
+    uint32_t zv[4];   // the four waves' votes on the mip1 tile (non-zero: some RGB half is not 0x0000)
 
-    // the tile's horizontal 1:1 sums; ends with a barrier (out() may follow directly)
-    __device__ __forceinline__ void build(const DImg& S1, int X0, int Y0, int W0, int H0, int tid) {
+    // the tile's horizontal 1:1 sums; ends with a barrier (out() may follow directly). Called by all 256 lanes.
+    // zs (SOC_BLOOM_ZERO_SKIP): returns true, after the first barrier and without the sums, when every RGB half of the
+    // clamped mip1 tile is 0x0000: every output of the tile is then pack3(+0, +0, +0) (sums of fma(+0, w > 0, +0)), which
+    // the caller takes in place of out(). Workgroup-uniform.
+    __device__ __forceinline__ bool build(const DImg& S1, int X0, int Y0, int W0, int H0, int tid, bool zs) {
         const int mx0 = X0 - 1, my0 = Y0 - 1;
         const int sx0 = X0 / 2 - 3, sy0 = Y0 / 2 - 3;
-        load_tile<SW, SH>(S1, sx0, sy0, st, tid);
+        const uint32_t nz = load_tile<SW, SH>(S1, sx0, sy0, st, tid);
+        if (zs) {   // the vote rides on the barrier the tile needs anyway
+            const bool any = __ballot(nz != 0u) != 0ull;
+            if ((tid & 63) == 0) zv[tid >> 6] = any ? 1u : 0u;
+        }
         __syncthreads();
+        if (zs && __builtin_amdgcn_readfirstlane((int)(zv[0] | zv[1] | zv[2] | zv[3])) == 0) return true;
         // 1:2 horizontal: hr/hg/hb[sr][c] for mip0 column c (coordinate clamp(mx0 + c)) on mip1 tile row sr
         for (int i = tid; i < SH * MW; i += 256) {
             const int sr = i / MW, c = i - sr * MW;
@@ -115,6 +128,7 @@ struct Up10Tile {
             hb[r][c] = a.b;
         }
         __syncthreads();
+        return false;
     }
     // the 1:1 vertical of the outputs at tile row r, tile columns c, c + 1 (the chain stores pack3 of each)
     __device__ __forceinline__ void out(int r, int c, C3 (&o)[2]) const {

@@ -36,6 +36,7 @@ struct CompParams {
     const soc_globals* __restrict__ dg;  // device globals (lights), may be null when npl == nsl == 0
     int sky_external;      // 1: sky pixels (depth == 1) are written and binned by sky_compose_pair (second lane)
     float rw, rh;          // recip_rn(target extent) for the pixel-centre uv (div_rn)
+    int bloom_zero_skip;   // SOC_BLOOM_ZERO_SKIP: the in-kernel bloom skips its sums on all-zero mip1 tiles (BL)
 };
 
 __device__ __forceinline__ float fast_pow(float x, float y) {
@@ -299,11 +300,16 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
     if constexpr (BL) {   // every lane takes part in the tile's barriers; the pair's bloom as the chain stores it
         __shared__ Up10Tile<32, 16> bl;
         const int X0 = bx * 32, Y0 = by * 16;
-        bl.build(mip1, X0, Y0, target.w, target.h, threadIdx.x);
-        C3 o[2];
-        bl.out(y - Y0, x - X0, o);
-        const uint2 b0 = pack3(o[0]), b1 = pack3(o[1]);
-        e4 = uint4{b0.x, b0.y, b1.x, b1.y};
+        // an all-zero mip1 tile (SOC_BLOOM_ZERO_SKIP): the pair is pack3(+0, +0, +0) without the tile's sums
+        if (bl.build(mip1, X0, Y0, target.w, target.h, threadIdx.x, p.bloom_zero_skip != 0)) {
+            const uint2 b0 = pack3(C3{0.0f, 0.0f, 0.0f});
+            e4 = uint4{b0.x, b0.y, b0.x, b0.y};
+        } else {
+            C3 o[2];
+            bl.out(y - Y0, x - X0, o);
+            const uint2 b0 = pack3(o[0]), b1 = pack3(o[1]);
+            e4 = uint4{b0.x, b0.y, b1.x, b1.y};
+        }
     }
     if (inside) {
         // LIGHTS: the light sum of the lane's two pixels runs once, as packed pairs (light_sum<f2v>, the same bits per
@@ -517,6 +523,7 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
     p.swz = 0;   // row-major (the strip order measured 66 -> 77 us)
     p.rw = recip_rn(target.width);
     p.rh = recip_rn(target.height);
+    p.bloom_zero_skip = tuning_knob("SOC_BLOOM_ZERO_SKIP", 1) != 0;
     p.bins = nullptr;
     p.sky_external = 0;
     if ((p.npl || p.nsl) && !d_globals)
