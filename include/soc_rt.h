@@ -279,6 +279,20 @@ int soc_ssao_generation(const soc_globals* g, soc_img depth, soc_img normal, soc
 /* SSAOBlurTask (ssao_blur.inl:19-70, shader :91-106): 4x4 box, offsets -2..+1. R8 -> R8. */
 int soc_ssao_blur(const soc_globals* g, soc_img ssao, soc_img target, soc_stream stream);
 
+/* ScreenSpaceReflectionTask (screen_space_reflection.inl:26-70, shader :88-183): per pixel, a pixel whose
+ * metallic_roughness.y is below 0.01 copies its albedo; every other pixel reflects its view ray about the view-space
+ * normal and marches it through `depth` (up to 50 probes: a growing step until the ray passes behind the depth image,
+ * then a binary search), writing the albedo at the probe that comes within 0.05 of the depth image, or (0, 0, 0, 1)
+ * when none does (quirk Q13: the shader's fallback to the pixel's own albedo cannot fire). depth: D32F; normal, albedo,
+ * metallic_roughness, target: RGBA16F; all of the target's extent (at most 8192 x 8192). `steps` (optional, data NULL =
+ * none): R8 of the same extent, the raw byte per pixel: 0..49 the iteration of the hit, 50 a miss, 255 a copied pixel;
+ * the colours are the same bits with or without it. The reference runs the task every frame between SSAOBlur and
+ * CloudRendering (renderer.cpp:1081-1092) although nothing reads its image (composition.inl:213-216 is commented out);
+ * here it is opt-in: the default render graph does not run it (soc_renderer_add_screen_space_reflection). */
+int soc_screen_space_reflection(const soc_globals* g, soc_img depth, soc_img normal, soc_img albedo,
+                                soc_img metallic_roughness, soc_img target, soc_img steps /* data NULL = none */,
+                                soc_stream stream);
+
 /* CloudRenderingTask (cloud_rendering.inl:27-54, shader :441-481): atmosphere + volumetric clouds on
  * sky pixels (depth == 1), constant (0.2,0.4,1.0) elsewhere. `noise` is the 64x64 RGBA8 or R8
  * noise texture (assets/Clouds/noise.png, REPEAT). target: RGBA8_UNORM full-res (quirk Q6).
@@ -529,6 +543,17 @@ typedef int32_t (*soc_pass_callback)(void* user, const soc_globals* g, const soc
  * in another phase, bad resource id, more than SOC_PASS_MAX_USES uses. */
 int soc_renderer_add_pass(soc_renderer* r, const soc_pass_desc* desc, soc_pass_callback fn, void* user,
                           const char* before);
+/* Add the reference's ScreenSpaceReflection task (soc_screen_space_reflection) as a library-owned pass: name
+ * "ScreenSpaceReflection", group "Screen Space Reflections", phase PRE, reads {ALBEDO, NORMAL, DEPTH,
+ * metallic_roughness_resource}, writes {target_resource}; both resource ids in SOC_RES_USER0 .. SOC_RES_USER0 + 31 (the
+ * metallic-roughness image and the ssr image are not frame images: the caller owns them and keeps them alive). `steps`
+ * as in soc_screen_space_reflection (data NULL = none). before = NULL places it where the reference registers it
+ * (renderer.cpp:1081-1092): before the pass whose name begins with "CloudRendering". pass_flags: 0, or SOC_PASS_ASYNC to
+ * run it on the second lane. Like a caller pass it survives soc_renderer_set_raster_scene; errors as
+ * soc_renderer_add_pass. Opt-in: a renderer that never calls this runs no SSR. */
+int soc_renderer_add_screen_space_reflection(soc_renderer* r, soc_img metallic_roughness, soc_img target, soc_img steps,
+                                             int32_t metallic_roughness_resource, int32_t target_resource,
+                                             uint32_t pass_flags /* 0 or SOC_PASS_ASYNC */, const char* before);
 /* Declared uses of pass `index` as resource bitmasks (bit = enum soc_resource). */
 int soc_renderer_pass_uses(const soc_renderer* r, int32_t index, uint64_t* reads, uint64_t* writes);
 /* Derived dependencies of pass `index`: the indices of the earlier passes it must follow (ascending).

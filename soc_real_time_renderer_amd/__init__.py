@@ -27,7 +27,7 @@ LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("SOC_RT_LIB_VARIANT", "li
 
 __all__ = ["SocError", "lib", "img", "Globals", "Camera", "AutoExposure", "globals_defaults", "frame_update",
            "bloom_downsample", "bloom_upsample", "bloom_chain", "ssao_prepare_noise", "ssao_generation",
-           "ssao_blur", "cloud_rendering", "composition", "generate_luminance_histogram",
+           "ssao_blur", "screen_space_reflection", "cloud_rendering", "composition", "generate_luminance_histogram",
            "resolve_luminance_histogram", "temporal_antialiasing", "copy_image", "tone_mapping", "upload_globals",
            "Renderer", "read_image", "write_png", "write_exr", "FMT_RGBA16F", "FMT_D32F", "FMT_R8_UNORM", "FMT_RGBA8_UNORM", "FMT_RGBA8_SRGB",
            "FMT_RGBA32F", "PHASE_PRE_EXPOSURE", "PHASE_POST_EXPOSURE", "PHASE_ALL"]
@@ -240,6 +240,14 @@ def ssao_generation(g, depth, normal, target, noise_table=None, stream=None):
 
 def ssao_blur(g, ssao, target, stream=None):
     _check(lib().soc_ssao_blur(_gp(g), img(ssao), img(target), _stream(stream)), "ssao_blur")
+
+
+def screen_space_reflection(g, depth, normal, albedo, metallic_roughness, target, steps=None, stream=None):
+    """ScreenSpaceReflectionTask (soc_screen_space_reflection): RGBA16F `target` from the G-buffer and a caller-supplied
+    RGBA16F metallic-roughness image; `steps` (optional uint8 (H, W)) receives the per-pixel iteration of the hit
+    (0..49), 50 for a miss, 255 for a copied pixel. Opt-in: the default render graph does not run it."""
+    _check(lib().soc_screen_space_reflection(_gp(g), img(depth), img(normal), img(albedo), img(metallic_roughness),
+                                             img(target), img(steps), _stream(stream)), "screen_space_reflection")
 
 
 def cloud_rendering_workspace(width: int, height: int, device="cuda") -> torch.Tensor:
@@ -499,6 +507,23 @@ class Renderer:
         _check(lib().soc_renderer_add_pass(self.handle, C.byref(d), cb, None, before.encode() if before else None),
                "soc_renderer_add_pass")
         self._callbacks = getattr(self, "_callbacks", []) + [cb]    # keep the trampolines alive
+
+    def add_screen_space_reflection(self, metallic_roughness, target, steps=None, mr_resource="USER0",
+                                    target_resource="USER1", async_compute: bool = False,
+                                    before: Optional[str] = None) -> None:
+        """Register the reference's ScreenSpaceReflection task (soc_renderer_add_screen_space_reflection) as a
+        library-owned pass writing `target` (and `steps`) every frame: before `before`, or where the reference runs it
+        (before CloudRendering). mr_resource / target_resource: caller resources ("USER<k>" or ids). The tensors are
+        kept alive with the renderer."""
+        def rid(x):
+            if isinstance(x, str) and x.startswith("USER") and x[4:].isdigit():
+                return _abi.RES_USER0 + int(x[4:])
+            return _abi.RES[x] if isinstance(x, str) else int(x)
+        _check(lib().soc_renderer_add_screen_space_reflection(
+            self.handle, img(metallic_roughness), img(target), img(steps), rid(mr_resource), rid(target_resource),
+            _abi.PASS_ASYNC if async_compute else 0, before.encode() if before else None),
+            "soc_renderer_add_screen_space_reflection")
+        self._ssr_images = (metallic_roughness, target, steps)   # keep the images alive
 
     def pass_uses(self, index: int):
         """(reads, writes) of pass `index` as sets of resource names (ids >= 32 as 'USER<k>')."""

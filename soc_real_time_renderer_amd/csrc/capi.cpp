@@ -606,7 +606,8 @@ extern "C" int soc_upload_globals(const soc_globals* g, soc_globals* d_globals, 
 }
 
 // =================================================================================================
-// Render graph (renderer.cpp:929-1235, live passes only; SSR / Hi-Z / DOF are dead or disabled)
+// Render graph (renderer.cpp:929-1235, live passes only; SSR / Hi-Z / DOF are dead or disabled; SSR can be added as an
+// opt-in pass, soc_renderer_add_screen_space_reflection)
 //
 // Every pass declares the frame resources it reads and writes (the Daxa task-uses block,
 // e.g. composition.inl:10-21). The graph keeps the registration order, which is the reference's
@@ -637,8 +638,12 @@ struct soc_renderer {
     struct UserPass {
         soc_pass_desc desc;
         std::string name, group, before;
-        soc_pass_callback fn;
-        void* user;
+        soc_pass_callback fn = nullptr;
+        void* user = nullptr;
+        // a library-owned pass registered like a caller pass (soc_renderer_add_screen_space_reflection): no callback,
+        // its images here; `before_prefix`: the anchor is the first pass whose name begins with `before`
+        bool ssr = false, before_prefix = false;
+        soc_img ssr_mr{}, ssr_target{}, ssr_steps{};
     };
     soc_frame_images img{};
     soc_raster_scene scene{};
@@ -1019,16 +1024,25 @@ int insert_user_passes(soc_renderer* r) {
         p.flags = up.desc.flags;
         const soc_pass_callback fn = up.fn;
         void* user = up.user;
-        p.run = [r, fn, user](const soc_globals* g, hipStream_t s) {
-            const soc_frame_images v = callback_view(r);
-            const int32_t rc = fn(user, g, &v, (soc_stream)s);
-            return rc ? set_error(rc, "caller pass failed with %d", (int)rc) : (int)SOC_OK;
-        };
+        if (up.ssr) {
+            const soc_img mr = up.ssr_mr, target = up.ssr_target, steps = up.ssr_steps;
+            p.run = [r, mr, target, steps](const soc_globals* g, hipStream_t s) {
+                return soc_screen_space_reflection(g, r->img.depth, r->img.normal, r->img.albedo, mr, target, steps,
+                                                   (soc_stream)s);
+            };
+        } else {
+            p.run = [r, fn, user](const soc_globals* g, hipStream_t s) {
+                const soc_frame_images v = callback_view(r);
+                const int32_t rc = fn(user, g, &v, (soc_stream)s);
+                return rc ? set_error(rc, "caller pass failed with %d", (int)rc) : (int)SOC_OK;
+            };
+        }
         size_t at = r->passes.size();
         if (!up.before.empty()) {
             at = r->passes.size() + 1;
             for (size_t i = 0; i < r->passes.size(); ++i)
-                if (r->passes[i].name == up.before) { at = i; break; }
+                if (up.before_prefix ? r->passes[i].name.compare(0, up.before.size(), up.before) == 0
+                                     : r->passes[i].name == up.before) { at = i; break; }
             if (at > r->passes.size())
                 return set_error(SOC_E_INVALID_ARG, "soc_renderer_add_pass: no pass named \"%s\"", up.before.c_str());
             if (r->passes[at].phase != p.phase)
@@ -1584,10 +1598,9 @@ extern "C" int soc_renderer_set_raster_scene(soc_renderer* r, const soc_raster_s
     return SOC_OK;
 }
 
-extern "C" int soc_renderer_add_pass(soc_renderer* r, const soc_pass_desc* d, soc_pass_callback fn, void* user,
-                                     const char* before) {
-    if (!r || !d || !fn || !d->name || !d->name[0])
-        return set_error(SOC_E_INVALID_ARG, "soc_renderer_add_pass: null renderer, descriptor, callback or name");
+// Registers `up` (its callback, or a library-owned pass's images, already set) under the descriptor `d`: the
+// descriptor checks, the rebuild and the roll-back shared by soc_renderer_add_pass and the library-owned passes.
+static int register_user_pass(soc_renderer* r, const soc_pass_desc* d, soc_renderer::UserPass up, const char* before) {
     if (d->phase != SOC_PHASE_PRE_EXPOSURE && d->phase != SOC_PHASE_POST_EXPOSURE)
         return set_error(SOC_E_INVALID_ARG, "soc_renderer_add_pass: %s: phase must be PRE or POST", d->name);
     if (d->read_count < 0 || d->read_count > SOC_PASS_MAX_USES || d->write_count < 0 || d->write_count > SOC_PASS_MAX_USES)
@@ -1599,13 +1612,10 @@ extern "C" int soc_renderer_add_pass(soc_renderer* r, const soc_pass_desc* d, so
     }
     for (const auto& p : r->passes)
         if (p.name == d->name) return set_error(SOC_E_INVALID_ARG, "soc_renderer_add_pass: duplicate pass name \"%s\"", d->name);
-    soc_renderer::UserPass up;
     up.desc = *d;
     up.name = d->name;
     up.group = d->group ? d->group : "";
     up.before = before ? before : "";
-    up.fn = fn;
-    up.user = user;
     up.desc.name = nullptr;
     up.desc.group = nullptr;
     r->user_passes.push_back(up);
@@ -1617,6 +1627,59 @@ extern "C" int soc_renderer_add_pass(soc_renderer* r, const soc_pass_desc* d, so
     }
     if (r->flags & SOC_RENDERER_TIMING) return soc_renderer_set_pass_timing(r, -1, 1);
     return SOC_OK;
+}
+
+extern "C" int soc_renderer_add_pass(soc_renderer* r, const soc_pass_desc* d, soc_pass_callback fn, void* user,
+                                     const char* before) {
+    if (!r || !d || !fn || !d->name || !d->name[0])
+        return set_error(SOC_E_INVALID_ARG, "soc_renderer_add_pass: null renderer, descriptor, callback or name");
+    soc_renderer::UserPass up;
+    up.fn = fn;
+    up.user = user;
+    return register_user_pass(r, d, up, before);
+}
+
+// ScreenSpaceReflectionTask as the reference registers it (renderer.cpp:1081-1092: after SSAOBlur, before
+// CloudRendering), through the caller-pass machinery, so it is re-inserted by every graph rebuild.
+extern "C" int soc_renderer_add_screen_space_reflection(soc_renderer* r, soc_img metallic_roughness, soc_img target,
+                                                        soc_img steps, int32_t metallic_roughness_resource,
+                                                        int32_t target_resource, uint32_t pass_flags, const char* before) {
+    const char* fn = "soc_renderer_add_screen_space_reflection";
+    if (!r) return set_error(SOC_E_INVALID_ARG, "%s: null renderer", fn);
+    if (pass_flags & ~(uint32_t)SOC_PASS_ASYNC) return set_error(SOC_E_INVALID_ARG, "%s: pass_flags must be 0 or SOC_PASS_ASYNC", fn);
+    for (int32_t id : {metallic_roughness_resource, target_resource})
+        if (id < SOC_RES_USER0 || id >= SOC_RES_COUNT)
+            return set_error(SOC_E_INVALID_ARG, "%s: bad resource id %d (SOC_RES_USER0 .. SOC_RES_USER0 + 31)", fn, id);
+    if (metallic_roughness_resource == target_resource)
+        return set_error(SOC_E_INVALID_ARG, "%s: the metallic-roughness image and the target need two resource ids", fn);
+    int rc = check_img(metallic_roughness, SOC_FMT_RGBA16F, fn, "metallic_roughness");
+    if (!rc) rc = check_img(target, SOC_FMT_RGBA16F, fn, "target");
+    if (!rc && steps.data) rc = check_img(steps, SOC_FMT_R8_UNORM, fn, "steps");
+    if (rc) return rc;
+    const soc_img* same[] = {&metallic_roughness, &target, &steps};
+    for (const soc_img* im : same)
+        if (im->data && (im->width != r->img.depth.width || im->height != r->img.depth.height))
+            return set_error(SOC_E_SHAPE, "%s: image is %dx%d, the frame's depth %dx%d", fn, im->width, im->height,
+                             r->img.depth.width, r->img.depth.height);
+    soc_pass_desc d{};
+    d.name = "ScreenSpaceReflection";
+    d.group = "Screen Space Reflections";
+    d.phase = SOC_PHASE_PRE_EXPOSURE;
+    d.flags = pass_flags;
+    d.read_count = 4;
+    d.reads[0] = SOC_RES_ALBEDO;
+    d.reads[1] = SOC_RES_NORMAL;
+    d.reads[2] = SOC_RES_DEPTH;
+    d.reads[3] = metallic_roughness_resource;
+    d.write_count = 1;
+    d.writes[0] = target_resource;
+    soc_renderer::UserPass up;
+    up.ssr = true;
+    up.ssr_mr = metallic_roughness;
+    up.ssr_target = target;
+    up.ssr_steps = steps;
+    up.before_prefix = before == nullptr;
+    return register_user_pass(r, &d, up, before ? before : "CloudRendering");
 }
 
 extern "C" int soc_renderer_pass_uses(const soc_renderer* r, int32_t i, uint64_t* reads, uint64_t* writes) {

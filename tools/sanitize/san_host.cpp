@@ -143,6 +143,19 @@ void render_graph(const soc_globals& g, int W, int H) {
         d.phase = SOC_PHASE_POST_EXPOSURE;
         d.flags = SOC_PASS_ASYNC;
         expect(soc_renderer_add_pass(r, &d, count_pass, &calls, nullptr) == SOC_OK, "async post pass");
+        // the library-owned ScreenSpaceReflection pass: argument errors, the default anchor, a duplicate, the rebuilds below
+        const soc_img mr = im(W, H, SOC_FMT_RGBA16F, 8), ssr = im(W, H, SOC_FMT_RGBA16F, 8), none{};
+        const int U = SOC_RES_USER0;
+        expect(soc_renderer_add_screen_space_reflection(nullptr, mr, ssr, none, U, U + 1, 0, nullptr) != SOC_OK, "ssr: null renderer");
+        expect(soc_renderer_add_screen_space_reflection(r, none, ssr, none, U, U + 1, 0, nullptr) != SOC_OK, "ssr: null image");
+        expect(soc_renderer_add_screen_space_reflection(r, mr, ssr, none, SOC_RES_DEPTH, U + 1, 0, nullptr) != SOC_OK, "ssr: bad resource");
+        expect(soc_renderer_add_screen_space_reflection(r, mr, ssr, none, U, U + 1, 0, "NoSuchPass") != SOC_OK, "ssr: unknown anchor");
+        expect(soc_renderer_add_screen_space_reflection(r, mr, im(W / 2, H, SOC_FMT_RGBA16F, 8), none, U, U + 1, 0, nullptr) != SOC_OK,
+               "ssr: extent mismatch");
+        expect(soc_renderer_add_screen_space_reflection(r, mr, ssr, im(W, H, SOC_FMT_R8_UNORM, 1), U, U + 1, SOC_PASS_ASYNC, nullptr) == SOC_OK,
+               "ssr: add");
+        expect(soc_renderer_add_screen_space_reflection(r, mr, ssr, none, U, U + 1, 0, nullptr) != SOC_OK, "ssr: duplicate");
+        expect(soc_screen_space_reflection(&g, none, none, none, none, none, none, nullptr) != SOC_OK, "ssr: null images");
         soc_raster_scene sc;
         std::memset(&sc, 0, sizeof sc);
         sc.mesh.positions = sc.mesh.normals = sc.mesh.uvs = reinterpret_cast<const float*>(fake);
