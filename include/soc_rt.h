@@ -51,12 +51,22 @@ typedef enum soc_format {
     SOC_FMT_RGBA32F = 6      /* R32G32B32A32_SFLOAT, 16 B/px (debug / exact tone-map output)                     */
 } soc_format;
 
-/* A borrowed view of a 2-D image in device memory (host memory for the CPU oracle). */
+/* A borrowed view of a 2-D image in device memory (host memory for the CPU oracle): pitch-linear rows, so a view
+ * into a wider allocation (padded rows, a column offset) is an image. With bpp = bytes_per_pixel(format):
+ *  - `data` and `pitch_bytes` are multiples of bpp (every kernel loads and stores whole texels); an image that is
+ *    not is refused with SOC_E_INVALID_ARG. Nothing more is required: launchers choose wider loads / stores from
+ *    data % 16 and pitch_bytes % 16 themselves, with the same results.
+ *  - A pass writes only the bytes [y * pitch_bytes, y * pitch_bytes + width * bpp) of each row y of an image it
+ *    writes, and no byte of an image it only reads.
+ *  - The library may read, but never uses, the bytes between the rows up to data + pitch_bytes * height (a wide
+ *    load at a row's end, a buffer descriptor over the whole view): that range must be readable memory, whatever it
+ *    holds (NaN, another image's texels) does not reach any result.
+ * tests/test_gpu_views.py holds every pass to this on padded, offset and misaligned views. */
 typedef struct soc_img {
     void* data;
     int32_t width;
     int32_t height;
-    int32_t pitch_bytes; /* bytes between rows; >= width * bytes_per_pixel(format) */
+    int32_t pitch_bytes; /* bytes between rows; >= width * bpp and a multiple of bpp */
     int32_t format;      /* soc_format */
 } soc_img;
 

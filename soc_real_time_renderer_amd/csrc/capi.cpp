@@ -40,6 +40,11 @@ int check_img(const soc_img& im, int fmt, const char* pass, const char* what) {
                          im.width, im.height, im.pitch_bytes, im.format);
     if (fmt > 0 && im.format != fmt)
         return set_error(SOC_E_INVALID_ARG, "%s: %s image has format %d, expected %d", pass, what, im.format, fmt);
+    // every kernel loads and stores whole texels: the base and the pitch are multiples of the texel size
+    const int b = bytes_per_pixel(im.format);
+    if (reinterpret_cast<uintptr_t>(im.data) % (uintptr_t)b != 0 || im.pitch_bytes % b != 0)
+        return set_error(SOC_E_INVALID_ARG, "%s: %s image is not aligned to its %d-byte texels (data=%p pitch=%d)", pass,
+                         what, b, im.data, im.pitch_bytes);
     return SOC_OK;
 }
 

@@ -269,6 +269,14 @@ __global__ __launch_bounds__(kWorkgroup) void raster_clear_vis(unsigned long lon
     if (i < n) vis[i] = ((unsigned long long)__float_as_uint(1.0f) << 32) | KEY_EMPTY;
 }
 
+// One block row per image row: texels [0, width) of the row, never the bytes between the rows of a padded view.
+__global__ __launch_bounds__(kWorkgroup) void raster_clear_depth(char* depth, size_t pitch, int width, int height) {
+    const int x = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (x >= width) return;
+    for (int y = (int)blockIdx.y; y < height; y += (int)gridDim.y)
+        reinterpret_cast<float*>(depth + (size_t)y * pitch)[x] = 1.0f;
+}
+
 // The large triangles' entries are reserved once per workgroup: an LDS atomic gives each its offset in the workgroup's
 // share and one global atomic on the packed counter reserves the share (one returning atomic on the one counter per
 // wave cost ~40 us at 4K: the counter serialises them). The packed adds keep the entry slots and their tile ranges
@@ -1005,10 +1013,10 @@ extern "C" int soc_raster_depth(const soc_mesh* mesh, const float view_projectio
     if (!view_projection || !workspace || cull < 0 || cull > 2)
         return set_error(SOC_E_INVALID_ARG, "soc_raster_depth: null argument or bad cull mode");
     hipStream_t s = hs(stream);
-    // depth clear 1.0 (sun_shadow_draw.inl:71-74)
-    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(depth.data), __builtin_bit_cast(int, 1.0f),
-                          (size_t)depth.pitch_bytes / 4 * depth.height, s) != hipSuccess)
-        return set_error(SOC_E_HIP, "soc_raster_depth: clear failed");
+    // depth clear 1.0 (sun_shadow_draw.inl:71-74): the width texels of each row only, a padded view's bytes between
+    // the rows belong to the caller
+    launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)), kWorkgroup, 0, s,
+           static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
     RasterParams p = make_raster_params(mesh, view_projection, depth.width, depth.height, cull);
     p.depth_only = 1;
     p.bias_constant = bias_constant;

@@ -90,6 +90,47 @@ def test_argument_errors_without_gpu(soc):
         soc.cloud_rendering(g, None, None, None, stream=0)
 
 
+def test_images_not_aligned_to_their_texels_are_rejected_without_gpu(soc):
+    """Every kernel loads whole texels: an image whose base or pitch is no multiple of its texel size is refused with
+    SOC_E_INVALID_ARG and a message naming the pass and the image (no tensor view can be one: built by hand). One-byte
+    texels (R8) take any base and pitch; a view offset by whole texels passes this check."""
+    lib, E_ARG = soc.lib(), soc._abi.SOC_E_INVALID_ARG
+    g = soc.globals_defaults(64, 36)
+    hdr = np.zeros((37, 72, 4), np.float16)
+    out8 = np.zeros((37, 72, 4), np.uint8)
+    out32 = np.zeros((37, 72, 4), np.float32)
+    ae = np.zeros(257, np.int32)
+
+    def view(a, data_off=0, pitch_off=0, fmt=None):
+        v = soc.img(a[:36, 1:65], fmt)
+        return soc.SocImg(v.data + data_off, v.width, v.height, v.pitch_bytes + pitch_off, v.format)
+    for kw_c, kw_t, which in ((dict(data_off=4), {}, "color"), (dict(pitch_off=4), {}, "color"),
+                              (dict(data_off=2), {}, "color"), ({}, dict(data_off=2), "target"),
+                              ({}, dict(pitch_off=1), "target")):
+        rc = lib.soc_tone_mapping(C.byref(g), view(hdr, **kw_c), ae.ctypes.data, view(out8, **kw_t), None)
+        msg = lib.soc_last_error_string().decode()
+        assert rc == E_ARG and "soc_tone_mapping" in msg and which in msg and "aligned" in msg, (kw_c, kw_t, msg)
+    rc = lib.soc_tone_mapping(C.byref(g), view(hdr), ae.ctypes.data, view(out32, data_off=8), None)
+    assert rc == E_ARG and "target" in lib.soc_last_error_string().decode()
+    r8 = np.zeros((20, 40), np.uint8)
+    for data_off, pitch in ((1, 40), (0, 41), (3, 33)):
+        odd = soc.SocImg(soc.img(r8).data + data_off, 32, 18, pitch, soc.FMT_R8_UNORM)
+        # an R8 image is fine at any byte offset and pitch: the call gets past the image checks to the alias check
+        rc = lib.soc_ssao_blur(C.byref(g), odd, odd, None)
+        msg = lib.soc_last_error_string().decode()
+        assert rc == E_ARG and "aligned" not in msg and "alias" in msg, msg
+    depth = np.ones((37, 72), np.float32)
+    mesh = soc._abi.Mesh()
+    for f in ("positions", "normals", "uvs", "indices"):
+        setattr(mesh, f, 1)
+    mesh.vertex_count, mesh.triangle_count = 3, 1
+    vp = (C.c_float * 16)()
+    for kw in (dict(data_off=2), dict(pitch_off=2)):
+        rc = lib.soc_raster_depth(C.byref(mesh), vp, 2, 1.25, 1.75, view(depth, **kw), None, None)
+        msg = lib.soc_last_error_string().decode()
+        assert rc == E_ARG and "soc_raster_depth" in msg and "depth" in msg and "aligned" in msg, msg
+
+
 def test_block_shape_over_the_launch_bound_is_rejected_without_gpu(soc):
     """The launch-geometry check (soc_check_block_shape; every launcher applies it with its kernel's bound before the
     launch): round 3's 64 x 16 SSAO-blur block against the kernel's 256-lane bound is refused on the host with

@@ -47,6 +47,14 @@ def test_argument_errors(soc):
     for name in ("depth", "normal", "albedo", "mr", "steps"):
         rc, msg = _call(soc, g, im, **{name: soc.img(small[name])})
         assert rc == E_SHAPE and "soc_screen_space_reflection" in msg, name
+    # a base or a pitch that is no multiple of the texel size (no tensor view has one: built by hand)
+    for name in ("depth", "normal", "albedo", "mr", "target"):
+        ok = soc.img(im[name])
+        b = im[name].strides[1]
+        for data, pitch in ((ok.data + b // 2, ok.pitch_bytes), (ok.data, ok.pitch_bytes + b // 2)):
+            rc, msg = _call(soc, g, im, **{name: soc.SocImg(data, W, H - 1, pitch, ok.format)})
+            assert rc == E_ARG and "soc_screen_space_reflection" in msg and "aligned" in msg, (name, msg)
+            assert {"mr": "metallic_roughness"}.get(name, name) in msg
     # an extent above 8192 (one row: validation reads no texel)
     wide = _images(8193, 1)
     rc, msg = _call(soc, g, wide)
