@@ -163,7 +163,7 @@ typedef struct soc_globals {       /* shared.inl:47-131 */
     float ambient_occlussion_strength;
     float emissive_bloom_strength;
 
-    float focal_length;            /* depth of field (disabled in the reference graph) */
+    float focal_length;            /* depth of field (disabled in the reference graph; soc_depth_of_field) */
     float plane_in_focus;
     float aperture;
 
@@ -302,6 +302,30 @@ int soc_ssao_blur(const soc_globals* g, soc_img ssao, soc_img target, soc_stream
 int soc_screen_space_reflection(const soc_globals* g, soc_img depth, soc_img normal, soc_img albedo,
                                 soc_img metallic_roughness, soc_img target, soc_img steps /* data NULL = none */,
                                 soc_stream stream);
+
+/* The reference's depth-of-field task chain (depth_of_field.inl; its three add_task calls are commented out,
+ * renderer.cpp:1119-1153). Here it is opt-in: the default render graph does not run it (soc_renderer_add_depth_of_field).
+ *
+ * The chain is depth_of_field_image (renderer.cpp:346, 463-468): RGBA16F, floor(log2(max(W, H))) + 1 levels, level k of
+ * max(1, W >> k) x max(1, H >> k) texels, in soc_generate_mips's packed layout at 8 B per texel: level 0 at
+ * pitch_bytes (at least 8 W, a multiple of 8), level k >= 1 at data + pitch_bytes * H + sum_{1 <= j < k} 8 w_j h_j with
+ * tight rows. soc_depth_of_field_chain_bytes is the size of the whole allocation (0 for bad arguments: an extent
+ * outside 1..8192, a pitch below 8 W or no multiple of 8). */
+size_t soc_depth_of_field_chain_bytes(int32_t width, int32_t height, int32_t pitch_bytes);
+/* BlitImageToImage (depth_of_field.inl:16-48) and every MipMapping - i (:55-88, renderer.cpp:1127-1144): level 0 of
+ * `chain` becomes a bit copy of `color`, level k a LINEAR blit (vkCmdBlitImage) of level k - 1 with soc_generate_mips's
+ * taps and 8-bit weights, filtered in f32 and rounded to f16 nearest-even. `chain` is the RGBA16F view of level 0; its
+ * allocation is soc_depth_of_field_chain_bytes(width, height, pitch_bytes) long. color: RGBA16F of the same extent
+ * (at most 8192 x 8192) that does not overlap the chain's allocation. */
+int soc_depth_of_field_mips(soc_img color, soc_img chain, soc_stream stream);
+/* DepthOfFieldTask (depth_of_field.inl:104-155, shader :176-199): a pixel with depth < 1 becomes the mean of four
+ * textureGrad taps of the chain at uv +- (1 / W, 0) and uv +- (0, 1 / H), both gradients (c, c) with c = coc / max_coc
+ * from g's camera clips, focal_length, plane_in_focus and aperture, through depth_of_field_sampler (renderer.cpp:472-488:
+ * trilinear, REPEAT, max_lod past the last level), with alpha 1; any other pixel (NaN depth included) is the chain's
+ * level-0 texel, alpha kept (quirk Q14). depth: D32F; chain: as soc_depth_of_field_mips left it; target: RGBA16F; all of
+ * one extent. The target is never read, so it may be the image the chain was built from (the reference's arrangement:
+ * color_image); it may not overlap the chain's allocation (SOC_E_INVALID_ARG, "alias"). */
+int soc_depth_of_field(const soc_globals* g, soc_img depth, soc_img chain, soc_img target, soc_stream stream);
 
 /* CloudRenderingTask (cloud_rendering.inl:27-54, shader :441-481): atmosphere + volumetric clouds on
  * sky pixels (depth == 1), constant (0.2,0.4,1.0) elsewhere. `noise` is the 64x64 RGBA8 or R8
@@ -564,6 +588,16 @@ int soc_renderer_add_pass(soc_renderer* r, const soc_pass_desc* desc, soc_pass_c
 int soc_renderer_add_screen_space_reflection(soc_renderer* r, soc_img metallic_roughness, soc_img target, soc_img steps,
                                              int32_t metallic_roughness_resource, int32_t target_resource,
                                              uint32_t pass_flags /* 0 or SOC_PASS_ASYNC */, const char* before);
+/* Add the reference's depth-of-field tasks as two library-owned passes, both in group "Depth Of Field", phase PRE, on
+ * the main lane: "MipMapping" (soc_depth_of_field_mips: the blit and every level; reads {COLOR}, writes
+ * {chain_resource}) and, directly after it, "DepthOfField" (soc_depth_of_field; reads {chain_resource, DEPTH}, writes
+ * {COLOR}). `chain`: the caller-owned RGBA16F chain of the frame's extent, kept alive; chain_resource in SOC_RES_USER0 ..
+ * SOC_RES_USER0 + 31. before = NULL places the pair where the reference has them (renderer.cpp:1119-1153): directly
+ * before "GenerateLuminanceHistogram". Requires a renderer created with SOC_RENDERER_UNFUSED_HISTOGRAM: the fused pass
+ * bins the colour as Composition writes it, and the reference's histogram reads the blurred colour. Like caller passes
+ * they survive soc_renderer_set_raster_scene; on any error the graph is left as it was (errors as
+ * soc_renderer_add_pass). Opt-in: a renderer that never calls this runs no depth of field. */
+int soc_renderer_add_depth_of_field(soc_renderer* r, soc_img chain, int32_t chain_resource, const char* before);
 /* Declared uses of pass `index` as resource bitmasks (bit = enum soc_resource). */
 int soc_renderer_pass_uses(const soc_renderer* r, int32_t index, uint64_t* reads, uint64_t* writes);
 /* Derived dependencies of pass `index`: the indices of the earlier passes it must follow (ascending).

@@ -27,7 +27,8 @@ LIB_PATH = os.path.join(PKG_DIR, "lib", os.environ.get("SOC_RT_LIB_VARIANT", "li
 
 __all__ = ["SocError", "lib", "img", "Globals", "Camera", "AutoExposure", "globals_defaults", "frame_update",
            "bloom_downsample", "bloom_upsample", "bloom_chain", "ssao_prepare_noise", "ssao_generation",
-           "ssao_blur", "screen_space_reflection", "cloud_rendering", "composition", "generate_luminance_histogram",
+           "ssao_blur", "screen_space_reflection", "DepthOfFieldChain", "depth_of_field_chain", "depth_of_field_mips",
+           "depth_of_field", "cloud_rendering", "composition", "generate_luminance_histogram",
            "resolve_luminance_histogram", "temporal_antialiasing", "copy_image", "tone_mapping", "upload_globals",
            "Renderer", "read_image", "write_png", "write_exr", "FMT_RGBA16F", "FMT_D32F", "FMT_R8_UNORM", "FMT_RGBA8_UNORM", "FMT_RGBA8_SRGB",
            "FMT_RGBA32F", "PHASE_PRE_EXPOSURE", "PHASE_POST_EXPOSURE", "PHASE_ALL"]
@@ -248,6 +249,68 @@ def screen_space_reflection(g, depth, normal, albedo, metallic_roughness, target
     (0..49), 50 for a miss, 255 for a copied pixel. Opt-in: the default render graph does not run it."""
     _check(lib().soc_screen_space_reflection(_gp(g), img(depth), img(normal), img(albedo), img(metallic_roughness),
                                              img(target), img(steps), _stream(stream)), "screen_space_reflection")
+
+
+class DepthOfFieldChain:
+    """The RGBA16F mip chain of the depth-of-field passes (soc_depth_of_field_mips) in one flat uint8 buffer `buf` of
+    soc_depth_of_field_chain_bytes(width, height, pitch_bytes) bytes: `level0` is the (H, W, 4) float16 view the C ABI
+    takes (rows `pitch_bytes` apart), levels()[k] the tight view of level k."""
+
+    def __init__(self, buf, width: int, height: int, pitch_bytes: Optional[int] = None):
+        self.width, self.height = int(width), int(height)
+        self.pitch_bytes = int(pitch_bytes) if pitch_bytes is not None else 8 * self.width
+        n = int(lib().soc_depth_of_field_chain_bytes(self.width, self.height, self.pitch_bytes))
+        if n == 0 or buf.numel() != n or buf.dtype != torch.uint8 or not buf.is_contiguous():
+            raise ValueError(f"a {self.width}x{self.height} chain at pitch {self.pitch_bytes} needs a contiguous uint8 "
+                             f"buffer of {n} bytes")
+        self.buf = buf
+
+    def _view(self, offset, h, w, pitch):
+        rows = self.buf[offset:offset + pitch * (h - 1) + 8 * w].view(torch.float16)
+        return rows.as_strided((h, w, 4), (pitch // 2, 4, 1))
+
+    @property
+    def level0(self) -> torch.Tensor:
+        return self._view(0, self.height, self.width, self.pitch_bytes)
+
+    def level_shapes(self):
+        shapes, w, h = [], self.width, self.height
+        while True:
+            shapes.append((h, w))
+            if w == 1 and h == 1:
+                return shapes
+            w, h = max(1, w // 2), max(1, h // 2)
+
+    def levels(self):
+        out, off = [self.level0], self.pitch_bytes * self.height
+        for h, w in self.level_shapes()[1:]:
+            out.append(self._view(off, h, w, 8 * w))
+            off += 8 * w * h
+        return out
+
+
+def depth_of_field_chain(width: int, height: int, device="cuda") -> DepthOfFieldChain:
+    """A zeroed depth-of-field chain for a width x height frame (tight level 0)."""
+    n = int(lib().soc_depth_of_field_chain_bytes(int(width), int(height), 8 * int(width)))
+    if n == 0:
+        raise ValueError(f"depth_of_field_chain: bad extent {width}x{height}")
+    return DepthOfFieldChain(torch.zeros(n, dtype=torch.uint8, device=device), width, height)
+
+
+def _chain_img(chain) -> SocImg:
+    return img(chain.level0 if isinstance(chain, DepthOfFieldChain) else chain)
+
+
+def depth_of_field_mips(color, chain, stream=None):
+    """BlitImageToImage + every MipMapping task (soc_depth_of_field_mips): level 0 of `chain` (a DepthOfFieldChain) becomes
+    a bit copy of the RGBA16F `color`, level k the LINEAR blit of level k - 1."""
+    _check(lib().soc_depth_of_field_mips(img(color), _chain_img(chain), _stream(stream)), "depth_of_field_mips")
+
+
+def depth_of_field(g, depth, chain, target, stream=None):
+    """DepthOfFieldTask (soc_depth_of_field): RGBA16F `target` from the D32F depth and the chain; `target` may be the image
+    the chain was built from. Opt-in: the default render graph does not run it."""
+    _check(lib().soc_depth_of_field(_gp(g), img(depth), _chain_img(chain), img(target), _stream(stream)), "depth_of_field")
 
 
 def cloud_rendering_workspace(width: int, height: int, device="cuda") -> torch.Tensor:
@@ -524,6 +587,20 @@ class Renderer:
             _abi.PASS_ASYNC if async_compute else 0, before.encode() if before else None),
             "soc_renderer_add_screen_space_reflection")
         self._ssr_images = (metallic_roughness, target, steps)   # keep the images alive
+
+    def add_depth_of_field(self, chain, chain_resource="USER0", before: Optional[str] = None) -> None:
+        """Register the reference's depth-of-field tasks (soc_renderer_add_depth_of_field) as the library-owned passes
+        "MipMapping" and "DepthOfField": before `before`, or where the reference has them (before
+        GenerateLuminanceHistogram). Needs fused_histogram=False. `chain`: a DepthOfFieldChain of the frame's extent,
+        kept alive with the renderer; chain_resource: a caller resource ("USER<k>" or an id)."""
+        def rid(x):
+            if isinstance(x, str) and x.startswith("USER") and x[4:].isdigit():
+                return _abi.RES_USER0 + int(x[4:])
+            return _abi.RES[x] if isinstance(x, str) else int(x)
+        _check(lib().soc_renderer_add_depth_of_field(self.handle, _chain_img(chain), rid(chain_resource),
+                                                     before.encode() if before else None),
+               "soc_renderer_add_depth_of_field")
+        self._dof_chain = chain   # keep the chain alive
 
     def pass_uses(self, index: int):
         """(reads, writes) of pass `index` as sets of resource names (ids >= 32 as 'USER<k>')."""

@@ -212,6 +212,10 @@ FUNCTIONS = {
     "soc_ssao_blur": (_I, [_G, _IMG, _IMG, _P]),
     "soc_screen_space_reflection": (_I, [_G, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _P]),
     "soc_renderer_add_screen_space_reflection": (_I, [_P, _IMG, _IMG, _IMG, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]),
+    "soc_depth_of_field_chain_bytes": (C.c_size_t, [_I, _I, _I]),
+    "soc_depth_of_field_mips": (_I, [_IMG, _IMG, _P]),
+    "soc_depth_of_field": (_I, [_G, _IMG, _IMG, _IMG, _P]),
+    "soc_renderer_add_depth_of_field": (_I, [_P, _IMG, C.c_int32, C.c_char_p]),
     "soc_cloud_rendering_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32]),
     "soc_cloud_rendering": (_I, [_G, _IMG, _IMG, _IMG, _P, _P]),
     "soc_composition_luminance_histogram": (_I, [_G, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _P, _P, _P]),

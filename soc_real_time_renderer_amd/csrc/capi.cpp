@@ -611,8 +611,8 @@ extern "C" int soc_upload_globals(const soc_globals* g, soc_globals* d_globals, 
 }
 
 // =================================================================================================
-// Render graph (renderer.cpp:929-1235, live passes only; SSR / Hi-Z / DOF are dead or disabled; SSR can be added as an
-// opt-in pass, soc_renderer_add_screen_space_reflection)
+// Render graph (renderer.cpp:929-1235, live passes only; SSR / Hi-Z / DOF are dead or disabled; SSR and DOF can be added
+// as opt-in passes, soc_renderer_add_screen_space_reflection / soc_renderer_add_depth_of_field)
 //
 // Every pass declares the frame resources it reads and writes (the Daxa task-uses block,
 // e.g. composition.inl:10-21). The graph keeps the registration order, which is the reference's
@@ -649,6 +649,9 @@ struct soc_renderer {
         // its images here; `before_prefix`: the anchor is the first pass whose name begins with `before`
         bool ssr = false, before_prefix = false;
         soc_img ssr_mr{}, ssr_target{}, ssr_steps{};
+        // soc_renderer_add_depth_of_field's pair: 1 = "MipMapping" (the chain from COLOR), 2 = "DepthOfField"
+        int dof = 0;
+        soc_img dof_chain{};
     };
     soc_frame_images img{};
     soc_raster_scene scene{};
@@ -1035,6 +1038,16 @@ int insert_user_passes(soc_renderer* r) {
                 return soc_screen_space_reflection(g, r->img.depth, r->img.normal, r->img.albedo, mr, target, steps,
                                                    (soc_stream)s);
             };
+        } else if (up.dof) {
+            const soc_img chain = up.dof_chain;
+            if (up.dof == 1)
+                p.run = [r, chain](const soc_globals*, hipStream_t s) {
+                    return soc_depth_of_field_mips(r->img.color, chain, (soc_stream)s);
+                };
+            else
+                p.run = [r, chain](const soc_globals* g, hipStream_t s) {
+                    return soc_depth_of_field(g, r->img.depth, chain, r->img.color, (soc_stream)s);
+                };
         } else {
             p.run = [r, fn, user](const soc_globals* g, hipStream_t s) {
                 const soc_frame_images v = callback_view(r);
@@ -1685,6 +1698,61 @@ extern "C" int soc_renderer_add_screen_space_reflection(soc_renderer* r, soc_img
     up.ssr_steps = steps;
     up.before_prefix = before == nullptr;
     return register_user_pass(r, &d, up, before ? before : "CloudRendering");
+}
+
+// The reference's BlitImageToImage + MipMapping - i and DepthOfField (renderer.cpp:1119-1153: after Composition, before
+// GenerateLuminanceHistogram) as two library-owned passes through the caller-pass machinery.
+extern "C" int soc_renderer_add_depth_of_field(soc_renderer* r, soc_img chain, int32_t chain_resource, const char* before) {
+    const char* fn = "soc_renderer_add_depth_of_field";
+    if (!r) return set_error(SOC_E_INVALID_ARG, "%s: null renderer", fn);
+    if (!(r->flags & SOC_RENDERER_UNFUSED_HISTOGRAM))
+        return set_error(SOC_E_INVALID_ARG,
+                         "%s: the renderer needs SOC_RENDERER_UNFUSED_HISTOGRAM: the fused Composition+GenerateLuminanceHistogram "
+                         "pass bins the colour before the blur, the reference's histogram reads the blurred colour", fn);
+    if (chain_resource < SOC_RES_USER0 || chain_resource >= SOC_RES_COUNT)
+        return set_error(SOC_E_INVALID_ARG, "%s: bad resource id %d (SOC_RES_USER0 .. SOC_RES_USER0 + 31)", fn, chain_resource);
+    const int rc = check_img(chain, SOC_FMT_RGBA16F, fn, "chain");
+    if (rc) return rc;
+    const soc_img& color = r->img.color;
+    if (chain.width != color.width || chain.height != color.height)
+        return set_error(SOC_E_SHAPE, "%s: chain is %dx%d, the frame's colour %dx%d", fn, chain.width, chain.height, color.width,
+                         color.height);
+    const size_t bytes = soc_depth_of_field_chain_bytes(chain.width, chain.height, chain.pitch_bytes);
+    if (!bytes) return set_error(SOC_E_INVALID_ARG, "%s: extent %dx%d above 8192", fn, chain.width, chain.height);
+    const char* c0 = static_cast<const char*>(color.data);
+    const char* c1 = c0 + (size_t)color.pitch_bytes * (size_t)(color.height - 1) + (size_t)color.width * 8;
+    const char* b0 = static_cast<const char*>(chain.data);
+    if (c0 < b0 + bytes && b0 < c1)
+        return set_error(SOC_E_INVALID_ARG, "%s: the frame's colour may not alias the chain's allocation", fn);
+    const char* anchor = before ? before : "GenerateLuminanceHistogram";
+    soc_pass_desc d{};
+    d.name = "MipMapping";
+    d.group = "Depth Of Field";
+    d.phase = SOC_PHASE_PRE_EXPOSURE;
+    d.read_count = 1;
+    d.reads[0] = SOC_RES_COLOR;
+    d.write_count = 1;
+    d.writes[0] = chain_resource;
+    soc_renderer::UserPass up;
+    up.dof = 1;
+    up.dof_chain = chain;
+    int rc2 = register_user_pass(r, &d, up, anchor);
+    if (rc2) return rc2;
+    d.name = "DepthOfField";
+    d.read_count = 2;
+    d.reads[0] = chain_resource;
+    d.reads[1] = SOC_RES_DEPTH;
+    d.writes[0] = SOC_RES_COLOR;
+    up.dof = 2;
+    rc2 = register_user_pass(r, &d, up, anchor);
+    if (rc2) {   // roll the first pass back (register_user_pass set the error; its own roll-back left "MipMapping" in)
+        const std::string msg = soc_last_error_string();
+        r->user_passes.pop_back();
+        (void)build_graph(r);
+        if (r->flags & SOC_RENDERER_TIMING) (void)soc_renderer_set_pass_timing(r, -1, 1);
+        return set_error(rc2, "%s", msg.c_str());
+    }
+    return SOC_OK;
 }
 
 extern "C" int soc_renderer_pass_uses(const soc_renderer* r, int32_t i, uint64_t* reads, uint64_t* writes) {

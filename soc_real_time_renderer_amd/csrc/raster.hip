@@ -426,23 +426,6 @@ __device__ __forceinline__ void texel_row_pair(const DImg& im, int x0, int x1, i
     }
 }
 
-// REPEAT addressing for any extent (the sampling contract's 8-bit sub-texel weights).
-__device__ __forceinline__ Axis axis_repeat_any(float u, int n) {
-#pragma clang fp contract(off)
-    float t = u * (float)n;
-    t = t - 0.5f;
-    t = fminf(fmaxf(t, -4194304.0f), 4194304.0f);
-    const int fx = (int)floorf(t * 256.0f + 0.5f);
-    const int i = fx >> 8;
-    Axis a;
-    a.w = (float)(fx & 255) * (1.0f / 256.0f);
-    int r = i % n;
-    if (r < 0) r += n;
-    a.i0 = r;
-    a.i1 = (r + 1) % n;
-    return a;
-}
-
 // REPEAT axis of extent n: the power-of-two mask when n is one (every texture of the reference's assets),
 // else the general modulo; same taps and weight either way.
 __device__ __forceinline__ Axis axis_repeat_level(float u, int n) {

@@ -117,6 +117,41 @@ __device__ __forceinline__ Axis axis_repeat_pow2(float u, int n, int mask) {
     return a;
 }
 
+// REPEAT addressing for any extent (the sampling contract's 8-bit sub-texel weights).
+__device__ __forceinline__ Axis axis_repeat_any(float u, int n) {
+#pragma clang fp contract(off)
+    float t = u * (float)n;
+    t = t - 0.5f;
+    t = fminf(fmaxf(t, -4194304.0f), 4194304.0f);
+    const int fx = (int)floorf(t * 256.0f + 0.5f);
+    const int i = fx >> 8;
+    Axis a;
+    a.w = (float)(fx & 255) * (1.0f / 256.0f);
+    int r = i % n;
+    if (r < 0) r += n;
+    a.i0 = r;
+    a.i1 = (r + 1) % n;
+    return a;
+}
+
+// Blit sample axis (vkCmdBlitImage LINEAR; the texture chain of texture.hip and the depth-of-field chain of dof.hip):
+// destination texel x of n_dst -> source taps of n_src, clamp to edge, 8-bit weights.
+__device__ __forceinline__ Axis blit_axis(int x, int n_src, int n_dst) {
+#pragma clang fp contract(off)
+    const float t = ((float)(2 * x + 1) * (float)n_src) / (float)(2 * n_dst) - 0.5f;
+    const int fx = (int)floorf(t * 256.0f + 0.5f);
+    int i = fx >> 8;
+    float w = (float)(fx & 255) * (1.0f / 256.0f);
+    if (i < 0) { i = 0; w = 0.0f; }
+    else if (i >= n_src - 1) { i = n_src - 2; w = 1.0f; }
+    if (n_src == 1) { i = 0; w = 0.0f; }
+    Axis a;
+    a.i0 = i;
+    a.i1 = min(i + 1, n_src - 1);
+    a.w = w;
+    return a;
+}
+
 __device__ __forceinline__ float lerp_w(float a, float b, float w) {
 #pragma clang fp contract(off)
     return a * (1.0f - w) + b * w;

@@ -35,23 +35,6 @@ const SrgbTables& srgb_tables() {
     return t;
 }
 
-// Blit sample axis: destination texel x of n_dst -> source taps of n_src, clamp to edge, 8-bit weights.
-__device__ __forceinline__ Axis blit_axis(int x, int n_src, int n_dst) {
-#pragma clang fp contract(off)
-    const float t = ((float)(2 * x + 1) * (float)n_src) / (float)(2 * n_dst) - 0.5f;
-    const int fx = (int)floorf(t * 256.0f + 0.5f);
-    int i = fx >> 8;
-    float w = (float)(fx & 255) * (1.0f / 256.0f);
-    if (i < 0) { i = 0; w = 0.0f; }
-    else if (i >= n_src - 1) { i = n_src - 2; w = 1.0f; }
-    if (n_src == 1) { i = 0; w = 0.0f; }
-    Axis a;
-    a.i0 = i;
-    a.i1 = min(i + 1, n_src - 1);
-    a.w = w;
-    return a;
-}
-
 // sRGB code of a linear value, round(encode(c) * 255): the number of boundaries mid[1..255] <= c (binary search).
 __device__ __forceinline__ uint32_t srgb_encode_code(float c, const SrgbTables& t) {
     uint32_t k = 0;

@@ -156,6 +156,34 @@ void render_graph(const soc_globals& g, int W, int H) {
                "ssr: add");
         expect(soc_renderer_add_screen_space_reflection(r, mr, ssr, none, U, U + 1, 0, nullptr) != SOC_OK, "ssr: duplicate");
         expect(soc_screen_space_reflection(&g, none, none, none, none, none, none, nullptr) != SOC_OK, "ssr: null images");
+        // the library-owned depth-of-field pair: the chain at a fake address of its own (the frame's colour may not alias
+        // it); refused on a fused-histogram renderer, argument errors that leave the graph as it was, a duplicate
+        const soc_img chain{fake + (1 << 28), W, H, W * 8, SOC_FMT_RGBA16F};
+        const bool unfused = flags & SOC_RENDERER_UNFUSED_HISTOGRAM;
+        expect(soc_depth_of_field_chain_bytes(W, H, W * 8) > (size_t)W * H * 8, "dof: chain bytes");
+        expect(soc_depth_of_field_chain_bytes(W, H, W * 8 - 8) == 0 && soc_depth_of_field_chain_bytes(0, H, 8) == 0, "dof: bad chain");
+        expect(soc_renderer_add_depth_of_field(nullptr, chain, U + 2, nullptr) != SOC_OK, "dof: null renderer");
+        if (!unfused) {
+            expect(soc_renderer_add_depth_of_field(r, chain, U + 2, nullptr) != SOC_OK, "dof: fused histogram refused");
+        } else {
+            expect(soc_renderer_add_depth_of_field(r, none, U + 2, nullptr) != SOC_OK, "dof: null chain");
+            expect(soc_renderer_add_depth_of_field(r, mr, U + 2, nullptr) != SOC_OK, "dof: chain aliases the colour");
+            expect(soc_renderer_add_depth_of_field(r, chain, SOC_RES_COLOR, nullptr) != SOC_OK, "dof: bad resource");
+            expect(soc_renderer_add_depth_of_field(r, chain, U + 2, "NoSuchPass") != SOC_OK, "dof: unknown anchor");
+            expect(soc_renderer_add_depth_of_field(r, chain, U + 2, "ToneMapping") != SOC_OK, "dof: anchor in the other phase");
+            const int before_n = soc_renderer_pass_count(r);
+            expect(soc_renderer_add_depth_of_field(r, soc_img{chain.data, W / 2, H, W * 4, SOC_FMT_RGBA16F}, U + 2, nullptr) != SOC_OK,
+                   "dof: extent mismatch");
+            expect(soc_renderer_pass_count(r) == before_n, "dof: refusals leave the graph");
+            expect(soc_renderer_add_depth_of_field(r, chain, U + 2, nullptr) == SOC_OK, "dof: add");
+            expect(soc_renderer_pass_count(r) == before_n + 2, "dof: two passes");
+            expect(soc_renderer_add_depth_of_field(r, chain, U + 2, nullptr) != SOC_OK, "dof: duplicate");
+        }
+        expect(soc_depth_of_field_mips(none, none, nullptr) != SOC_OK, "dof mips: null images");
+        expect(soc_depth_of_field_mips(mr, mr, nullptr) != SOC_OK, "dof mips: colour aliases the chain");
+        expect(soc_depth_of_field(&g, none, none, none, nullptr) != SOC_OK, "dof: null images");
+        expect(soc_depth_of_field(nullptr, fi.depth, chain, mr, nullptr) != SOC_OK, "dof: null globals");
+        expect(soc_depth_of_field(&g, fi.depth, chain, chain, nullptr) != SOC_OK, "dof: target aliases the chain");
         soc_raster_scene sc;
         std::memset(&sc, 0, sizeof sc);
         sc.mesh.positions = sc.mesh.normals = sc.mesh.uvs = reinterpret_cast<const float*>(fake);
