@@ -448,7 +448,11 @@ typedef struct soc_renderer soc_renderer;
  * on the second lane (CloudRendering: it writes only CLOUDS) may then start before the fork, i.e. before the caller's
  * stream reaches this frame: the clouds of frame N+1 overlap the composition / TAA of frame N. Same results. The
  * second lane's intermediate CLOUDS image may then already hold the next frame's clouds when work the caller queued
- * between two calls reads it: a caller that reads CLOUDS between frames leaves the flag off. */
+ * between two calls reads it: a caller that reads CLOUDS between frames leaves the flag off. The transform array of a
+ * draw scene (soc_renderer_set_draw_scene) is not such an input image: its readers (DepthPrepass and GBufferGeneration
+ * on the caller's stream, SunShadowDraw on the second lane, which has a ring edge on the previous frame's Composition
+ * and so always waits for the fork) follow everything the caller queued before the call, so the caller may rewrite
+ * it on its stream between frames with the flag set. */
 #define SOC_RENDERER_STATIC_INPUTS 256
 /* Velocity history by slot rotation instead of a copy. The reference copies the velocity image into
  * previous_velocity after TAA every frame (CopyImageTask, renderer.cpp:1185-1189; without this flag the TAA launch
@@ -623,8 +627,9 @@ int32_t soc_renderer_pass_lane(const soc_renderer* r, int32_t index);
  * (equal depth: the later triangle wins), culling by facing. Front faces are CLOCKWISE in the framebuffer
  * (Vulkan area a < 0): the reference culls FRONT for its glTF meshes, whose outward faces are counter-
  * clockwise as seen, so its pipelines' (Daxa default, not in the mount) front face must be clockwise.
- * Edge functions are homogeneous (2DH), so geometry behind the eye needs no clipping. The scene is one
- * mesh (the reference's draws concatenated). */
+ * Edge functions are homogeneous (2DH), so geometry behind the eye needs no clipping. A soc_mesh is
+ * one mesh with one transform (the reference's draws concatenated); a scene of per-entity draws with their own
+ * transforms is a soc_draw_scene ("Draw scenes" below). */
 typedef struct soc_mesh {              /* device pointers (Vertex, shared.inl:152-157) */
     const float* positions;            /* vertex_count x float3, object space */
     const float* normals;              /* vertex_count x float3, object space */
@@ -761,6 +766,88 @@ typedef struct soc_raster_scene {
 /* NULL: clear. With shadow = 1 the renderer allocates a second raster workspace (soc_raster_workspace_size of the mesh)
  * for the sun shadow draw, which then runs on its second lane beside the depth prepass and the G-buffer. */
 int soc_renderer_set_raster_scene(soc_renderer* r, const soc_raster_scene* scene);
+
+/* --- Draw scenes: per-entity draws with their own transforms ------------------------------------
+ * The reference draws a scene of entities: GBufferGenerationTask (g_buffer_generation.inl:111-144), DepthPrepassTask
+ * (depth_prepass.inl) and SunShadowDrawTask (sun_shadow_draw.inl) walk scene->iterate, bind every mesh entity's
+ * TransformComponent buffer (model_matrix, normal_matrix) and issue one draw_indexed {index_count, first_index,
+ * vertex_offset} per primitive with the primitive's material in the push constant. A draw scene is that loop as
+ * data: shared vertex arrays, one index array, a host array of draws and a device array of transforms. Results are
+ * those of the serial draw loop: the global triangle id of draw d's local triangle t is sum(triangle_count of the
+ * draws before d) + t; the visibility key stays depth bits << 32 | (0xFFFFFFFE - id), so at equal depth the later
+ * draw, and within a draw the later triangle, wins (LESS_OR_EQUAL in draw order). Every vertex of a draw goes through
+ * the single-mesh vertex arithmetic with that draw's matrices (the same bits as a soc_mesh holding the draw). Culling,
+ * depth clipping, bias and clear values are unchanged. Velocity follows the reference: the previous clip position uses
+ * the CURRENT model matrix (g_buffer_generation.inl:171); per-object motion vectors are out of scope. */
+typedef struct soc_transform {         /* TransformComponent buffer; what soc_scene_update writes per entity */
+    float model_matrix[16];            /* column-major */
+    float normal_matrix[16];           /* its upper 3x3 transforms normals */
+} soc_transform;
+typedef struct soc_draw {              /* one draw_indexed of one entity (g_buffer_generation.inl:135-143) */
+    int32_t first_index;               /* first element of the index array */
+    int32_t triangle_count;            /* index_count / 3 of the primitive (0: an empty draw) */
+    int32_t vertex_offset;             /* signed, added to every fetched index */
+    int32_t first_vertex, vertex_count;/* the vertex range the draw's offset indices must fall in */
+    int32_t transform;                 /* index into the transform array */
+    int32_t material;                  /* primitive.material_index: one material for every triangle of the draw */
+} soc_draw;
+/* Non-indexed primitives are expressed with an identity index range. Several draws may name one vertex range with
+ * different transforms (two entities, one Model): each gets its own transformed copy of the range per frame. */
+typedef struct soc_draw_scene {
+    const float* positions;            /* device, vertex_count x float3, object space */
+    const float* normals;              /* device, vertex_count x float3 (the G-buffer resolve needs it) */
+    const float* uvs;                  /* device, vertex_count x float2 (the G-buffer resolve needs it) */
+    const uint32_t* indices;           /* device, index_count entries */
+    int32_t vertex_count, index_count;
+    const soc_draw* draws;             /* HOST array, draw order */
+    int32_t draw_count;
+    int32_t transform_count;
+    const soc_transform* transforms;   /* device; rewritten by the caller between frames (no rebuild needed) */
+    int32_t material_count;            /* every draw's material is below it */
+    int32_t pad;
+    void* workspace;                   /* device, soc_draw_workspace_size(draws, draw_count) bytes, 256-byte aligned */
+} soc_draw_scene;
+/* Workspace of a draw list (pure host; 0 on bad input: null draws, a negative count or field, more than 2^31 - 1
+ * triangles or transformed vertices in all). Layout: the static tables built by
+ * soc_draw_scene_build (per transformed-vertex slot its source vertex, transform and uv; the index buffer rebased to
+ * the slots in global triangle order; the per-triangle material), then one single-mesh raster workspace
+ * (soc_raster_workspace_size of the slot and triangle totals) per view: the camera's (soc_raster_visibility_draws,
+ * soc_gbuffer_resolve_draws) and the sun's (soc_raster_depth_draws), so the two may run on different streams. There
+ * is one slot per (draw, vertex of its range). */
+size_t soc_draw_workspace_size(const soc_draw* draws, int32_t draw_count);
+/* Load-time build of the static tables, run once and again whenever the draws, the indices or the uvs change (not
+ * when the transforms do). Everything the host can check is checked before the first HIP call (SOC_E_INVALID_ARG:
+ * null pointers, bad counts; SOC_E_SHAPE: first_index + 3 triangle_count > index_count, a vertex range outside
+ * vertex_count, transform >= transform_count, material >= material_count, 0xFFFFFFFE triangles or more). The build
+ * then validates ON THE DEVICE that every fetched index + vertex_offset lies in the draw's [first_vertex, first_vertex
+ * + vertex_count) before any kernel addresses a vertex with it, synchronises `stream` to read the result back and
+ * returns SOC_E_SHAPE with the first offending draw in soc_last_error_string(). The library remembers the outcome per
+ * workspace: the *_draws entry points refuse (without a launch) a scene that was not built, whose description changed
+ * since, or whose build failed. Call soc_draw_scene_release before freeing or reusing the workspace. */
+int soc_draw_scene_build(const soc_draw_scene* scene, soc_stream stream);
+/* Forgets what the library remembers of the scene's workspace (NULL or an unknown workspace: no-op). */
+void soc_draw_scene_release(const soc_draw_scene* scene);
+/* The single-mesh entry points' twins, with the scene in place of the mesh (same arguments otherwise, no workspace:
+ * the scene carries it). The draw-aware vertex kernels run per call with the transforms as they are on `stream`;
+ * the triangle and pixel kernels are the single-mesh ones, on the rebased tables. soc_raster_visibility_draws and
+ * soc_gbuffer_resolve_draws share the camera view's buffers (order them on one stream, resolve after visibility);
+ * soc_raster_depth_draws uses the sun view's. The resolve always uses the per-vertex workspace. */
+int soc_raster_visibility_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                uint64_t* visibility, int32_t width, int32_t height, int32_t clear, soc_stream stream);
+int soc_raster_depth_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                           float bias_constant, float bias_slope, soc_img depth, soc_stream stream);
+int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene, const soc_material* d_materials,
+                              int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
+                              soc_img emissive, soc_img normal, soc_img velocity, soc_stream stream);
+/* The raster head from a draw scene: DepthPrepass, SunShadowDraw (with `shadow`), GBufferGeneration, with the names,
+ * groups, declared uses and lanes soc_renderer_set_raster_scene gives. Replaces a scene set by
+ * soc_renderer_set_raster_scene and the other way round; NULL clears. The renderer copies the struct and the draw
+ * array; the device arrays stay caller-owned. It keeps the device pointer to the transforms: the caller rewrites that
+ * array on its own stream between frames and the next soc_renderer_execute sees it, like every frame input (written
+ * on the caller's stream before the call). The sun shadow draw reads it on the second lane behind the call's fork,
+ * also under SOC_RENDERER_STATIC_INPUTS (see there). */
+int soc_renderer_set_draw_scene(soc_renderer* r, const soc_draw_scene* scene, const soc_material* d_materials,
+                                int32_t material_count, int32_t shadow, uint64_t* visibility);
 
 /* --- Headless output and metrics (replaces the swapchain present of tone_mapping.inl:
  * 172-176 and the ImGui "GPU Metric" window of renderer.cpp:769-806) ------------------------------- */

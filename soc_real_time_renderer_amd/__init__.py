@@ -482,6 +482,18 @@ class Renderer:
         self._scene = (mesh, d_materials, visibility, workspace)   # keep the arrays alive
         _check(lib().soc_renderer_set_raster_scene(self.handle, C.byref(sc)), "soc_renderer_set_raster_scene")
 
+    def set_draw_scene(self, scene, d_materials, material_count: int, visibility, shadow: bool = True):
+        """Raster head from a raster.DrawScene (per-entity draws with their own transforms); replaces a
+        set_raster_scene scene and the other way round; None clears. The renderer keeps the device pointer to
+        scene.transforms: rewrite it in place (raster.update_transforms) between frames."""
+        if scene is None:
+            _check(lib().soc_renderer_set_draw_scene(self.handle, None, None, 0, 0, None), "soc_renderer_set_draw_scene")
+            self._scene = None
+            return
+        self._scene = (scene, d_materials, visibility)   # keep the arrays alive
+        _check(lib().soc_renderer_set_draw_scene(self.handle, C.byref(scene.struct), _ptr(d_materials), int(material_count),
+                                                 int(bool(shadow)), _ptr(visibility)), "soc_renderer_set_draw_scene")
+
     def metrics_json(self, frame: int = 0) -> str:
         """The last frame's GPU-metric record (renderer.cpp:769-806) as a JSON string (needs timing and a
         completed stream)."""

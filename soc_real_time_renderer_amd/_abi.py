@@ -140,6 +140,26 @@ class RasterScene(C.Structure):
                 ("visibility", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class Transform(C.Structure):
+    """soc_transform: the TransformComponent buffer of one entity (what soc_scene_update writes)."""
+    _fields_ = [("model_matrix", Mat4), ("normal_matrix", Mat4)]
+
+
+class Draw(C.Structure):
+    """soc_draw: one draw_indexed of one entity (g_buffer_generation.inl:135-143)."""
+    _fields_ = [("first_index", C.c_int32), ("triangle_count", C.c_int32), ("vertex_offset", C.c_int32),
+                ("first_vertex", C.c_int32), ("vertex_count", C.c_int32), ("transform", C.c_int32),
+                ("material", C.c_int32)]
+
+
+class DrawSceneStruct(C.Structure):
+    """soc_draw_scene: shared vertex arrays, one index array, host draws, device transforms, workspace."""
+    _fields_ = [("positions", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p), ("indices", C.c_void_p),
+                ("vertex_count", C.c_int32), ("index_count", C.c_int32), ("draws", C.POINTER(Draw)),
+                ("draw_count", C.c_int32), ("transform_count", C.c_int32), ("transforms", C.c_void_p),
+                ("material_count", C.c_int32), ("pad", C.c_int32), ("workspace", C.c_void_p)]
+
+
 ENTITY_POINT_LIGHT, ENTITY_SPOT_LIGHT = 1, 2
 
 
@@ -180,7 +200,8 @@ MATERIAL_PAIRED_TEXELS = 16
 STRUCTS = {"soc_img": SocImg, "soc_globals": Globals, "soc_sun_info": SunInfo, "soc_point_light": PointLight,
            "soc_spot_light": SpotLight, "soc_auto_exposure": AutoExposure, "soc_camera": Camera,
            "soc_frame_images": FrameImages, "soc_mesh": Mesh, "soc_material": Material,
-           "soc_raster_scene": RasterScene, "soc_pass_desc": PassDesc, "soc_entity": Entity}
+           "soc_raster_scene": RasterScene, "soc_pass_desc": PassDesc, "soc_entity": Entity,
+           "soc_transform": Transform, "soc_draw": Draw, "soc_draw_scene": DrawSceneStruct}
 
 _I = C.c_int
 _P = C.c_void_p
@@ -272,6 +293,16 @@ FUNCTIONS = {
                                    C.c_int32, _P, _P]),
     "soc_raster_depth": (_I, [C.POINTER(Mesh), C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float, _IMG, _P, _P]),
     "soc_gbuffer_resolve": (_I, [_G, C.POINTER(Mesh), _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _P, _P]),
+    "soc_draw_workspace_size": (C.c_size_t, [C.POINTER(Draw), C.c_int32]),
+    "soc_draw_scene_build": (_I, [C.POINTER(DrawSceneStruct), _P]),
+    "soc_draw_scene_release": (None, [C.POINTER(DrawSceneStruct)]),
+    "soc_raster_visibility_draws": (_I, [C.POINTER(DrawSceneStruct), C.POINTER(C.c_float), C.c_int32, _P, C.c_int32,
+                                         C.c_int32, C.c_int32, _P]),
+    "soc_raster_depth_draws": (_I, [C.POINTER(DrawSceneStruct), C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float,
+                                    _IMG, _P]),
+    "soc_gbuffer_resolve_draws": (_I, [_G, C.POINTER(DrawSceneStruct), _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG, _IMG,
+                                       _P]),
+    "soc_renderer_set_draw_scene": (_I, [_P, C.POINTER(DrawSceneStruct), _P, C.c_int32, C.c_int32, _P]),
 }
 
 # not in the public header: test hooks

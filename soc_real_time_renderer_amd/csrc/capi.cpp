@@ -220,6 +220,13 @@ const FieldInfo kFields[] = {
     F(soc_material, normal_image), F(soc_material, max_anisotropy), F(soc_material, pad2), F(soc_material, paired_texels),
     F(soc_raster_scene, mesh), F(soc_raster_scene, materials), F(soc_raster_scene, material_count),
     F(soc_raster_scene, shadow), F(soc_raster_scene, visibility), F(soc_raster_scene, workspace),
+    F(soc_transform, model_matrix), F(soc_transform, normal_matrix),
+    F(soc_draw, first_index), F(soc_draw, triangle_count), F(soc_draw, vertex_offset), F(soc_draw, first_vertex),
+    F(soc_draw, vertex_count), F(soc_draw, transform), F(soc_draw, material),
+    F(soc_draw_scene, positions), F(soc_draw_scene, normals), F(soc_draw_scene, uvs), F(soc_draw_scene, indices),
+    F(soc_draw_scene, vertex_count), F(soc_draw_scene, index_count), F(soc_draw_scene, draws), F(soc_draw_scene, draw_count),
+    F(soc_draw_scene, transform_count), F(soc_draw_scene, transforms), F(soc_draw_scene, material_count),
+    F(soc_draw_scene, pad), F(soc_draw_scene, workspace),
     F(soc_entity, position), F(soc_entity, rotation), F(soc_entity, scale), F(soc_entity, components),
     F(soc_entity, color), F(soc_entity, intensity), F(soc_entity, cut_off), F(soc_entity, outer_cut_off),
     F(soc_pass_desc, name), F(soc_pass_desc, group), F(soc_pass_desc, phase), F(soc_pass_desc, flags),
@@ -244,6 +251,9 @@ extern "C" size_t soc_abi_sizeof(const char* t) {
     if (s == "soc_mesh") return sizeof(soc_mesh);
     if (s == "soc_material") return sizeof(soc_material);
     if (s == "soc_raster_scene") return sizeof(soc_raster_scene);
+    if (s == "soc_transform") return sizeof(soc_transform);
+    if (s == "soc_draw") return sizeof(soc_draw);
+    if (s == "soc_draw_scene") return sizeof(soc_draw_scene);
     if (s == "soc_pass_desc") return sizeof(soc_pass_desc);
     if (s == "soc_entity") return sizeof(soc_entity);
     return 0;
@@ -656,6 +666,12 @@ struct soc_renderer {
     soc_frame_images img{};
     soc_raster_scene scene{};
     bool has_scene = false;
+    // soc_renderer_set_draw_scene: the raster head from a draw scene instead of `scene` (has_scene is set with either).
+    // The struct and the draw array are copies (draw_scene.draws points into `draws`); of `scene` only materials,
+    // material_count, shadow and visibility are used then.
+    soc_draw_scene draw_scene{};
+    std::vector<soc_draw> draws;
+    bool has_draws = false;
     std::vector<Pass> passes;
     std::vector<UserPass> user_passes;
     uint32_t flags = 0;
@@ -780,15 +796,22 @@ void build_raster_passes(soc_renderer* r) {
     add_pass(r, "DepthPrepass", "Depth Prepass", pre, 0, res_mask({SOC_RES_VISIBILITY}),
              [r](const soc_globals* g, hipStream_t s) {
                  const soc_img& d = r->img.depth;
+                 if (r->has_draws)
+                     return soc_raster_visibility_draws(&r->draw_scene, g->camera_projection_view_matrix, SOC_CULL_FRONT,
+                                                        r->scene.visibility, d.width, d.height, 1, (soc_stream)s);
                  return soc_raster_visibility(&r->scene.mesh, g->camera_projection_view_matrix, SOC_CULL_FRONT,
                                               r->scene.visibility, d.width, d.height, 1, r->scene.workspace, (soc_stream)s);
              });
     // With its own workspace the shadow draw reads nothing the main lane writes in the frame: it runs on the second lane
     // beside the depth prepass and the G-buffer (SOC_RENDERER_SHADOW_LANE=0: on the main lane, in the shared workspace).
-    const bool shadow_lane = r->shadow_ws && tuning_knob("SOC_RENDERER_SHADOW_LANE", 1);
+    // A draw scene's workspace holds the sun view's buffers itself.
+    const bool shadow_lane = (r->has_draws || r->shadow_ws) && tuning_knob("SOC_RENDERER_SHADOW_LANE", 1);
     if (r->scene.shadow)
         add_pass(r, "SunShadowDraw", "Shadows", pre, 0, res_mask({SOC_RES_SUN_SHADOW}),
                  [r, shadow_lane](const soc_globals* g, hipStream_t s) {
+                     if (r->has_draws)
+                         return soc_raster_depth_draws(&r->draw_scene, g->sun_info.projection_view_matrix, SOC_CULL_BACK,
+                                                       1.25f, 1.75f, r->img.shadow, (soc_stream)s);
                      return soc_raster_depth(&r->scene.mesh, g->sun_info.projection_view_matrix, SOC_CULL_BACK, 1.25f,
                                              1.75f, r->img.shadow, shadow_lane ? r->shadow_ws : r->scene.workspace,
                                              (soc_stream)s);
@@ -798,6 +821,10 @@ void build_raster_passes(soc_renderer* r) {
              res_mask({SOC_RES_ALBEDO, SOC_RES_EMISSIVE, SOC_RES_NORMAL, SOC_RES_VELOCITY, SOC_RES_DEPTH}),
              [r](const soc_globals* g, hipStream_t s) {
                  const soc_frame_images& I = r->img;
+                 if (r->has_draws)
+                     return soc_gbuffer_resolve_draws(g, &r->draw_scene, r->scene.materials, r->scene.material_count,
+                                                      r->scene.visibility, I.depth, I.albedo, I.emissive, I.normal,
+                                                      frame_velocity(r), (soc_stream)s);
                  return soc_gbuffer_resolve(g, &r->scene.mesh, r->scene.materials, r->scene.material_count,
                                             r->scene.visibility, I.depth, I.albedo, I.emissive, I.normal,
                                             frame_velocity(r), r->scene.workspace, (soc_stream)s);
@@ -1609,7 +1636,39 @@ extern "C" int soc_renderer_set_raster_scene(soc_renderer* r, const soc_raster_s
         }
     }
     r->has_scene = scene != nullptr;
+    r->has_draws = false;
+    r->draws.clear();
     if (scene) r->scene = *scene;
+    int rc = build_graph(r);
+    if (rc) return rc;
+    if (r->flags & SOC_RENDERER_TIMING) return soc_renderer_set_pass_timing(r, -1, 1);
+    return SOC_OK;
+}
+
+extern "C" int soc_renderer_set_draw_scene(soc_renderer* r, const soc_draw_scene* scene, const soc_material* d_materials,
+                                           int32_t material_count, int32_t shadow, uint64_t* visibility) {
+    if (!r) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_draw_scene: null renderer");
+    if (!scene) return soc_renderer_set_raster_scene(r, nullptr);
+    if (!d_materials || material_count <= 0 || !visibility || !scene->positions || !scene->normals || !scene->uvs ||
+        !scene->indices || !scene->transforms || !scene->workspace || scene->draw_count < 0 ||
+        (scene->draw_count > 0 && !scene->draws))
+        return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_draw_scene: incomplete scene");
+    if (material_count < scene->material_count)
+        return set_error(SOC_E_SHAPE, "soc_renderer_set_draw_scene: %d materials, the scene's draws name up to %d", material_count,
+                         scene->material_count);
+    if (shadow && !r->img.shadow.data)
+        return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_draw_scene: shadow pass needs images.shadow");
+    // the draws' own checks (ranges, the build's outcome) are the *_draws entry points', every frame: a scene rebuilt or
+    // never built is refused there, before any launch
+    r->draws.assign(scene->draws, scene->draws + scene->draw_count);
+    r->draw_scene = *scene;
+    r->draw_scene.draws = r->draws.data();
+    r->scene = soc_raster_scene{};
+    r->scene.materials = d_materials;
+    r->scene.material_count = material_count;
+    r->scene.shadow = shadow != 0;
+    r->scene.visibility = visibility;
+    r->has_scene = r->has_draws = true;
     int rc = build_graph(r);
     if (rc) return rc;
     if (r->flags & SOC_RENDERER_TIMING) return soc_renderer_set_pass_timing(r, -1, 1);

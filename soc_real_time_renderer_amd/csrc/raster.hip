@@ -21,6 +21,12 @@
 // The coverage, depth and barycentric arithmetic is written without FMA contraction and matches the
 // oracle's (oracle/soc_oracle.c, soc_oracle_raster_*) operation for operation, so the visibility buffer
 // and the depth images are bit-exact against it.
+// A scene of per-entity draws with their own transforms (soc_draw_scene) runs the same triangle and pixel kernels on
+// tables built at load time, behind draw-aware versions of the two vertex kernels: see "Draw scenes" below.
+#include <mutex>
+#include <unordered_map>
+#include <vector>
+
 #include "luminance.hpp"
 #include "soc_internal.hpp"
 
@@ -961,6 +967,304 @@ int launch_raster(const soc_mesh* mesh, const RasterParams& p, void* target, siz
     return check_launch(pass);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Draw scenes (soc_rt.h "Draw scenes"): per-entity draws with their own transforms
+// ------------------------------------------------------------------------------------------------
+// The reference's draw loop (g_buffer_generation.inl:111-144, depth_prepass.inl, sun_shadow_draw.inl) as tables. The
+// topology is static until the draws change, the transforms and so every transformed vertex change per frame:
+//   load time  draws_build_slots  one lane per transformed-vertex slot (one per (draw, vertex of its range)):
+//                                 {source vertex, transform} and the source vertex's uv
+//              draws_build_tris   one lane per global triangle (draw order): validates its three fetched indices +
+//                                 vertex_offset against the draw's vertex range, rebases them to the draw's slots and
+//                                 writes the triangle's material
+//   per frame  raster_setup_draws / gbuffer_vertex_setup_draws: raster_setup / gbuffer_vertex_setup per slot, with the
+//                                 slot's source vertex and its draw's matrices (clip_vertex / vertex_data as they are)
+// raster_small, raster_big and gbuffer_resolve<true> then run UNCHANGED on a single-mesh view of the tables (slot count
+// as the vertex count, the rebased indices, the slot uvs, the per-triangle materials): a triangle's global id is its
+// position in the rebased index buffer, so the keys and the tie rule are the serial draw loop's.
+struct DrawRec {   // device copy of a draw with its prefix sums
+    int32_t first_index, triangle_count, vertex_offset, first_vertex, vertex_count, transform, material;
+    int32_t slot_base, triangle_base;
+};
+
+// workspace: [u32 first failing draw (0xFFFFFFFF: none), pad to 256] [uint2 slots[S]] [float2 slot uvs[S]]
+//            [u32 rebased indices[3 T]] [u32 triangle materials[T]] [DrawRec[D]] [raster workspace of (S, T)] x 2 views
+struct DrawWorkspace {
+    uint32_t* flag;
+    uint2* slots;         // {source vertex, transform}
+    float2* slot_uvs;
+    uint32_t* indices;
+    uint32_t* materials;
+    DrawRec* draws;
+    void* view[2];        // 0: the camera (visibility, G-buffer vertex data), 1: the sun (depth)
+};
+constexpr uint32_t DRAWS_OK = 0xFFFFFFFFu;
+
+struct DrawTotals { long long slots = 0, triangles = 0; };
+
+// Slot and triangle totals of a draw list; false on a null list, a negative count or field, or totals beyond int32.
+bool draw_totals(const soc_draw* draws, int32_t draw_count, DrawTotals& t) {
+    if (draw_count < 0 || (draw_count > 0 && !draws)) return false;
+    for (int32_t d = 0; d < draw_count; ++d) {
+        if (draws[d].triangle_count < 0 || draws[d].vertex_count < 0 || draws[d].first_vertex < 0 || draws[d].first_index < 0)
+            return false;
+        t.slots += draws[d].vertex_count;
+        t.triangles += draws[d].triangle_count;
+    }
+    return t.slots <= 0x7FFFFFFFll && t.triangles <= 0x7FFFFFFFll;
+}
+
+size_t draw_tables_bytes(long long S, long long T, int32_t D) {
+    size_t off = 256;
+    off = align_up(off + (size_t)S * 8, 256);
+    off = align_up(off + (size_t)S * 8, 256);
+    off = align_up(off + (size_t)T * 12, 256);
+    off = align_up(off + (size_t)T * 4, 256);
+    off = align_up(off + (size_t)D * sizeof(DrawRec), 256);
+    return off;
+}
+
+DrawWorkspace draw_carve(void* ws, long long S, long long T, int32_t D) {
+    char* p = static_cast<char*>(ws);
+    DrawWorkspace w;
+    w.flag = reinterpret_cast<uint32_t*>(p);
+    size_t off = 256;
+    w.slots = reinterpret_cast<uint2*>(p + off);
+    off = align_up(off + (size_t)S * 8, 256);
+    w.slot_uvs = reinterpret_cast<float2*>(p + off);
+    off = align_up(off + (size_t)S * 8, 256);
+    w.indices = reinterpret_cast<uint32_t*>(p + off);
+    off = align_up(off + (size_t)T * 12, 256);
+    w.materials = reinterpret_cast<uint32_t*>(p + off);
+    off = align_up(off + (size_t)T * 4, 256);
+    w.draws = reinterpret_cast<DrawRec*>(p + off);
+    off = align_up(off + (size_t)D * sizeof(DrawRec), 256);
+    const size_t view = align_up(soc_raster_workspace_size((int32_t)S, (int32_t)T), 256);
+    w.view[0] = p + off;
+    w.view[1] = p + off + view;
+    return w;
+}
+
+// The last draw whose base (slot_base or triangle_base) is <= i. Empty draws share their base with the next draw, so
+// the last one at a base is the draw that owns item i. n >= 1.
+template <int32_t DrawRec::*BASE>
+__device__ __forceinline__ int find_draw(const DrawRec* __restrict__ draws, int n, int i) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (draws[mid].*BASE <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kWorkgroup) void draws_build_slots(const float* __restrict__ uvs, DrawWorkspace ws, int draw_count,
+                                                         int slot_count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= slot_count) return;
+    const DrawRec d = ws.draws[find_draw<&DrawRec::slot_base>(ws.draws, draw_count, i)];
+    // the host checked first_vertex + vertex_count <= the scene's vertex_count: src addresses the vertex arrays
+    const uint32_t src = (uint32_t)(d.first_vertex + (i - d.slot_base));
+    ws.slots[i] = uint2{src, (uint32_t)d.transform};
+    if (uvs) ws.slot_uvs[i] = float2{uvs[2 * src], uvs[2 * src + 1]};
+}
+
+// Every read is bounded by what the host checked (first_index + 3 triangle_count <= index_count); the fetched index
+// itself addresses nothing here: it is only compared and rebased. A triangle with an index outside its draw's vertex
+// range records its draw (the smallest wins) and is written as a degenerate triangle of slot 0.
+__global__ __launch_bounds__(kWorkgroup) void draws_build_tris(const uint32_t* __restrict__ indices, DrawWorkspace ws,
+                                                        int draw_count, int triangle_count) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= triangle_count) return;
+    const int di = find_draw<&DrawRec::triangle_base>(ws.draws, draw_count, id);
+    const DrawRec d = ws.draws[di];
+    const size_t at = (size_t)d.first_index + 3 * (size_t)(id - d.triangle_base);
+    uint32_t out[3];
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) {
+        const long long v = (long long)indices[at + k] + d.vertex_offset - d.first_vertex;
+        ok = ok && v >= 0 && v < d.vertex_count;
+        out[k] = (uint32_t)(d.slot_base + (int)v);
+    }
+    if (!ok) {
+        atomicMin(ws.flag, (uint32_t)di);
+        out[0] = out[1] = out[2] = 0u;
+    }
+    ws.indices[3 * (size_t)id] = out[0];
+    ws.indices[3 * (size_t)id + 1] = out[1];
+    ws.indices[3 * (size_t)id + 2] = out[2];
+    ws.materials[id] = (uint32_t)d.material;
+}
+
+// Calls f with the transform of this lane's slot. Consecutive slots of one draw share a transform: when every lane of
+// the wave names the same one (a wave inside one draw), 32 lanes fetch its 32 floats once (one coalesced 128-byte load)
+// into the wave's LDS record and every lane reads the matrices from there (broadcast reads); a wave that straddles draws
+// loads per lane from global memory. The same values reach the same arithmetic either way. Every lane of the
+// workgroup must call this, once per kernel (lanes past the last slot pass the last slot's transform). The explicit
+// forms without LDS (a branch on a readfirstlane index, a waterfall loop over the wave's distinct transforms) do not
+// survive the compiler: it folds both back into the per-lane load (SOC_DRAWS_LDS_TRANSFORM=0 builds that form: A/B).
+#ifndef SOC_DRAWS_LDS_TRANSFORM
+#define SOC_DRAWS_LDS_TRANSFORM 1
+#endif
+template <typename F>
+__device__ __forceinline__ void with_slot_transform(const soc_transform* __restrict__ xf, uint32_t t, F&& f) {
+#if !SOC_DRAWS_LDS_TRANSFORM
+    f(xf[t]);
+#else
+    static_assert(sizeof(soc_transform) == 32 * sizeof(float), "one float per lane of half a wave");
+    __shared__ soc_transform wave_xf[kWorkgroup / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t first = __builtin_amdgcn_readfirstlane(t);
+    const bool uniform = __all(t == first);
+    if (uniform && lane < 32)
+        reinterpret_cast<float*>(&wave_xf[wave])[lane] = reinterpret_cast<const float*>(&xf[first])[lane];
+    __syncthreads();
+    if (uniform) f(wave_xf[wave]);
+    else f(xf[t]);
+#endif
+}
+
+__device__ __forceinline__ Mat4 mat4_of(const float* __restrict__ m) {
+    Mat4 r;
+    for (int i = 0; i < 16; ++i) r.m[i] = m[i];
+    return r;
+}
+
+// raster_setup per transformed-vertex slot (p.vertex_count slots).
+__global__ __launch_bounds__(kWorkgroup) void raster_setup_draws(const float* __restrict__ pos, const uint2* __restrict__ slots,
+                                                          const soc_transform* __restrict__ xf, Workspace ws, RasterParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *ws.counter = 0ull;
+    if (p.vertex_count == 0) return;
+    const bool live = i < p.vertex_count;
+    const uint2 sl = slots[live ? i : p.vertex_count - 1];
+    with_slot_transform(xf, sl.y, [&](const soc_transform& t) {
+        const float4 v = clip_vertex(pos, (int)sl.x, mat4_of(t.model_matrix), p.vp, p.width, p.height);
+        if (live) ws.screen[i] = v;
+    });
+}
+
+// gbuffer_vertex_setup per transformed-vertex slot: vertex_data of the slot's source vertex with its draw's model and
+// normal matrix (mesh: the scene's vertex arrays).
+__global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup_draws(soc_mesh mesh, const uint2* __restrict__ slots,
+                                                                  const soc_transform* __restrict__ xf, int slot_count,
+                                                                  float4* __restrict__ vd, ResolveParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (slot_count == 0) return;
+    const bool live = i < slot_count;
+    const uint2 sl = slots[live ? i : slot_count - 1];
+    with_slot_transform(xf, sl.y, [&](const soc_transform& t) {
+        ResolveParams q = p;
+        q.model = mat4_of(t.model_matrix);
+        const float* nm = t.normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
+        q.normal3 = Mat3{{nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]}};
+        const VtxData d = vertex_data(mesh, sl.x, q);
+        if (!live) return;
+        vd[4 * i] = d.s;
+        vd[4 * i + 1] = d.n;
+        vd[4 * i + 2] = d.cc;
+        vd[4 * i + 3] = d.pc;
+    });
+}
+
+// What the library remembers of a built workspace: a fingerprint of everything the static tables were built from, the
+// totals, and the first draw the device validation rejected (DRAWS_OK: none).
+struct DrawBuilt {
+    uint64_t fingerprint;
+    uint32_t failed_draw;
+};
+std::mutex g_draws_mutex;
+std::unordered_map<const void*, DrawBuilt> g_draws_built;
+
+uint64_t fnv1a(uint64_t h, const void* data, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(data);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+uint64_t draw_fingerprint(const soc_draw_scene* sc) {
+    uint64_t h = 14695981039346656037ull;
+    h = fnv1a(h, &sc->indices, sizeof sc->indices);
+    h = fnv1a(h, &sc->uvs, sizeof sc->uvs);
+    h = fnv1a(h, &sc->vertex_count, sizeof sc->vertex_count);
+    h = fnv1a(h, &sc->index_count, sizeof sc->index_count);
+    h = fnv1a(h, &sc->draw_count, sizeof sc->draw_count);
+    if (sc->draw_count > 0) h = fnv1a(h, sc->draws, (size_t)sc->draw_count * sizeof(soc_draw));
+    return h;
+}
+
+// Everything the host can check of a draw scene, before any HIP call.
+int check_draw_scene(const soc_draw_scene* sc, const char* pass, bool attributes, DrawTotals& tot) {
+    if (!sc) return set_error(SOC_E_INVALID_ARG, "%s: null scene", pass);
+    if (!sc->positions || !sc->indices || !sc->transforms || !sc->workspace || sc->vertex_count < 0 || sc->index_count < 0 ||
+        sc->draw_count < 0 || (sc->draw_count > 0 && !sc->draws) || sc->transform_count <= 0 || sc->material_count <= 0)
+        return set_error(SOC_E_INVALID_ARG, "%s: null positions / indices / draws / transforms / workspace or bad counts", pass);
+    if (attributes && (!sc->normals || !sc->uvs))
+        return set_error(SOC_E_INVALID_ARG, "%s: the G-buffer resolve needs normals and uvs", pass);
+    if (reinterpret_cast<uintptr_t>(sc->workspace) % 256)
+        return set_error(SOC_E_INVALID_ARG, "%s: the workspace must be 256-byte aligned", pass);
+    long long triangles = 0;
+    for (int32_t i = 0; i < sc->draw_count; ++i) {
+        const soc_draw& d = sc->draws[i];
+        if (d.triangle_count < 0 || d.vertex_count < 0 || d.first_vertex < 0 || d.first_index < 0)
+            return set_error(SOC_E_INVALID_ARG, "%s: draw %d: negative first_index, triangle_count or vertex range", pass, i);
+        if ((long long)d.first_index + 3ll * d.triangle_count > sc->index_count)
+            return set_error(SOC_E_SHAPE, "%s: draw %d: first_index %d + 3 x %d triangles exceed index_count %d", pass, i,
+                             d.first_index, d.triangle_count, sc->index_count);
+        if ((long long)d.first_vertex + d.vertex_count > sc->vertex_count)
+            return set_error(SOC_E_SHAPE, "%s: draw %d: vertex range [%d, %d + %d) exceeds vertex_count %d", pass, i,
+                             d.first_vertex, d.first_vertex, d.vertex_count, sc->vertex_count);
+        if (d.transform < 0 || d.transform >= sc->transform_count)
+            return set_error(SOC_E_SHAPE, "%s: draw %d: transform %d outside the %d transforms", pass, i, d.transform,
+                             sc->transform_count);
+        if (d.material < 0 || d.material >= sc->material_count)
+            return set_error(SOC_E_SHAPE, "%s: draw %d: material %d outside the %d materials", pass, i, d.material,
+                             sc->material_count);
+        triangles += d.triangle_count;
+        if (triangles >= 0xFFFFFFFEll)
+            return set_error(SOC_E_SHAPE, "%s: too many triangles for the visibility key", pass);
+    }
+    tot = DrawTotals();
+    if (!draw_totals(sc->draws, sc->draw_count, tot))
+        return set_error(SOC_E_SHAPE, "%s: more than 2^31 - 1 triangles or transformed vertices", pass);
+    return SOC_OK;
+}
+
+// check_draw_scene, then the build record of the workspace: only a scene whose build succeeded, unchanged since.
+int check_built_scene(const soc_draw_scene* sc, const char* pass, bool attributes, DrawTotals& tot) {
+    int rc = check_draw_scene(sc, pass, attributes, tot);
+    if (rc) return rc;
+    DrawBuilt b{};
+    {
+        std::lock_guard<std::mutex> lock(g_draws_mutex);
+        const auto it = g_draws_built.find(sc->workspace);
+        if (it == g_draws_built.end())
+            return set_error(SOC_E_INVALID_ARG, "%s: the scene's workspace was not built (soc_draw_scene_build)", pass);
+        b = it->second;
+    }
+    if (b.fingerprint != draw_fingerprint(sc))
+        return set_error(SOC_E_INVALID_ARG, "%s: the draws, indices or uvs changed since soc_draw_scene_build", pass);
+    if (b.failed_draw != DRAWS_OK)
+        return set_error(SOC_E_SHAPE, "%s: the scene failed its build: draw %u fetches an index outside its vertex range", pass,
+                         b.failed_draw);
+    return SOC_OK;
+}
+
+int launch_raster_draws(const soc_draw_scene* sc, const DrawTotals& tot, int view, RasterParams p, void* target, size_t pitch,
+                        hipStream_t s, const char* pass) {
+    const DrawWorkspace dw = draw_carve(sc->workspace, tot.slots, tot.triangles, sc->draw_count);
+    const int S = (int)tot.slots, T = (int)tot.triangles;
+    p.vertex_count = S;
+    p.triangle_count = T;
+    Workspace ws = carve(dw.view[view], S, T);
+    launch("raster_setup_draws", kWorkgroup, raster_setup_draws, ceil_div(max(S, 1), 256), kWorkgroup, 0, s, sc->positions,
+           dw.slots, sc->transforms, ws, p);
+    if (T > 0) {
+        launch("raster_small", kWorkgroup, raster_small, ceil_div(T, 256), kWorkgroup, 0, s, dw.indices, ws, p, target, pitch);
+        launch("raster_big", kWorkgroup, raster_big, 2048, kWorkgroup, 0, s, dw.indices, ws, p, target, pitch);
+    }
+    return check_launch(pass);
+}
+
 }  // namespace
 }  // namespace soc
 
@@ -1007,42 +1311,55 @@ extern "C" int soc_raster_depth(const soc_mesh* mesh, const float view_projectio
     return launch_raster(mesh, p, depth.data, (size_t)depth.pitch_bytes, workspace, s, "raster_depth");
 }
 
+// The checks, parameters and launch geometry soc_gbuffer_resolve and soc_gbuffer_resolve_draws share: everything of
+// ResolveParams but the matrices of the mesh (model, normal3) and its triangle count.
+static int resolve_prepare(const char* pass, const soc_globals* g, const soc_material* d_materials, int32_t material_count,
+                           const uint64_t* visibility, const soc_img& depth, const soc_img& albedo, const soc_img& emissive,
+                           const soc_img& normal, const soc_img& velocity, ResolveParams& p, dim3& grd) {
+    int rc = check_img(depth, SOC_FMT_D32F, pass, "depth");
+    if (!rc) rc = check_img(albedo, SOC_FMT_RGBA16F, pass, "albedo");
+    if (!rc) rc = check_img(emissive, SOC_FMT_RGBA16F, pass, "emissive");
+    if (!rc) rc = check_img(normal, SOC_FMT_RGBA16F, pass, "normal");
+    if (!rc) rc = check_img(velocity, SOC_FMT_RGBA16F, pass, "velocity");
+    if (rc) return rc;
+    if (!g || !d_materials || material_count <= 0 || !visibility)
+        return set_error(SOC_E_INVALID_ARG, "%s: null globals / materials / visibility", pass);
+    const int W = depth.width, H = depth.height;
+    for (const soc_img* im : {&albedo, &emissive, &normal, &velocity})
+        if (im->width != W || im->height != H)
+            return set_error(SOC_E_SHAPE, "%s: G-buffer images must share the depth extent", pass);
+    p.vp = mat4(g->camera_projection_view_matrix);
+    p.prev_vp = mat4(g->camera_previous_projection_view_matrix);
+    p.width = W;
+    p.height = H;
+    p.material_count = material_count;
+    p.tex_pairs = tuning_knob("SOC_GB_TEX_PAIRS", 1);
+    p.paired = tuning_knob("SOC_GB_PAIRED", 1);
+    p.wave_shape = tuning_knob("SOC_GB_WAVE", 2);   // 8 x 8-pixel waves: 687 -> 626 us at 4K (profiles/r04_probe_gbuffer_wave.txt)
+    grd = dim3(ceil_div(W, 64), ceil_div(H, 4));
+    if (p.wave_shape == 2) grd = dim3(ceil_div(W, 32), ceil_div(H, 8));
+    else if (p.wave_shape == 3) grd = dim3(ceil_div(W, 16), ceil_div(H, 16));
+    else if (p.wave_shape == 4) grd = dim3(ceil_div(W, 8), ceil_div(H, 32));
+    else if (p.wave_shape != 0 && p.wave_shape != 1) return set_error(SOC_E_INVALID_ARG, "%s: SOC_GB_WAVE %d", pass, p.wave_shape);
+    return SOC_OK;
+}
+
 extern "C" int soc_gbuffer_resolve(const soc_globals* g, const soc_mesh* mesh, const soc_material* d_materials,
                                    int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
                                    soc_img emissive, soc_img normal, soc_img velocity, void* workspace,
                                    soc_stream stream) {
     int rc = check_mesh(mesh, "soc_gbuffer_resolve", true);
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "soc_gbuffer_resolve", "depth");
-    if (!rc) rc = check_img(albedo, SOC_FMT_RGBA16F, "soc_gbuffer_resolve", "albedo");
-    if (!rc) rc = check_img(emissive, SOC_FMT_RGBA16F, "soc_gbuffer_resolve", "emissive");
-    if (!rc) rc = check_img(normal, SOC_FMT_RGBA16F, "soc_gbuffer_resolve", "normal");
-    if (!rc) rc = check_img(velocity, SOC_FMT_RGBA16F, "soc_gbuffer_resolve", "velocity");
     if (rc) return rc;
-    if (!g || !d_materials || material_count <= 0 || !visibility)
-        return set_error(SOC_E_INVALID_ARG, "soc_gbuffer_resolve: null globals / materials / visibility");
-    const int W = depth.width, H = depth.height;
-    for (const soc_img* im : {&albedo, &emissive, &normal, &velocity})
-        if (im->width != W || im->height != H)
-            return set_error(SOC_E_SHAPE, "soc_gbuffer_resolve: G-buffer images must share the depth extent");
     ResolveParams p{};
+    dim3 blk(64, 4), grd;
+    rc = resolve_prepare("soc_gbuffer_resolve", g, d_materials, material_count, visibility, depth, albedo, emissive, normal,
+                         velocity, p, grd);
+    if (rc) return rc;
     p.model = mat4(mesh->model_matrix);
-    p.vp = mat4(g->camera_projection_view_matrix);
-    p.prev_vp = mat4(g->camera_previous_projection_view_matrix);
     const float* nm = mesh->normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
     const float n3[9] = {nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]};
     for (int i = 0; i < 9; ++i) p.normal3.m[i] = n3[i];
-    p.width = W;
-    p.height = H;
     p.triangle_count = mesh->triangle_count;
-    p.material_count = material_count;
-    p.tex_pairs = tuning_knob("SOC_GB_TEX_PAIRS", 1);
-    p.paired = tuning_knob("SOC_GB_PAIRED", 1);
-    p.wave_shape = tuning_knob("SOC_GB_WAVE", 2);   // 8 x 8-pixel waves: 687 -> 626 us at 4K (profiles/r04_probe_gbuffer_wave.txt)
-    dim3 blk(64, 4), grd(ceil_div(W, 64), ceil_div(H, 4));
-    if (p.wave_shape == 2) grd = dim3(ceil_div(W, 32), ceil_div(H, 8));
-    else if (p.wave_shape == 3) grd = dim3(ceil_div(W, 16), ceil_div(H, 16));
-    else if (p.wave_shape == 4) grd = dim3(ceil_div(W, 8), ceil_div(H, 32));
-    else if (p.wave_shape != 0 && p.wave_shape != 1) return set_error(SOC_E_INVALID_ARG, "soc_gbuffer_resolve: SOC_GB_WAVE %d", p.wave_shape);
     const unsigned long long* vis = reinterpret_cast<const unsigned long long*>(visibility);
     if (workspace) {   // per-vertex outputs once, then the per-pixel resolve reads them
         const Workspace ws = carve(workspace, mesh->vertex_count, mesh->triangle_count);
@@ -1055,4 +1372,150 @@ extern "C" int soc_gbuffer_resolve(const soc_globals* g, const soc_mesh* mesh, c
                                                             dimg(emissive), dimg(normal), dimg(velocity), nullptr, p);
     }
     return check_launch("gbuffer_resolve");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Draw scenes: entry points
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t soc_draw_workspace_size(const soc_draw* draws, int32_t draw_count) {
+    DrawTotals t;
+    if (!draw_totals(draws, draw_count, t)) return 0;
+    return draw_tables_bytes(t.slots, t.triangles, draw_count) +
+           2 * align_up(soc_raster_workspace_size((int32_t)t.slots, (int32_t)t.triangles), 256);
+}
+
+extern "C" void soc_draw_scene_release(const soc_draw_scene* scene) {
+    if (!scene || !scene->workspace) return;
+    std::lock_guard<std::mutex> lock(g_draws_mutex);
+    g_draws_built.erase(scene->workspace);
+}
+
+extern "C" int soc_draw_scene_build(const soc_draw_scene* scene, soc_stream stream) {
+    DrawTotals tot;
+    int rc = check_draw_scene(scene, "soc_draw_scene_build", false, tot);
+    if (rc) return rc;
+    soc_draw_scene_release(scene);   // until this build has finished the workspace holds no built scene
+    const int D = scene->draw_count, S = (int)tot.slots, T = (int)tot.triangles;
+    const DrawWorkspace dw = draw_carve(scene->workspace, tot.slots, tot.triangles, D);
+    std::vector<DrawRec> recs((size_t)D);
+    int32_t slot_base = 0, triangle_base = 0;
+    for (int i = 0; i < D; ++i) {
+        const soc_draw& d = scene->draws[i];
+        recs[i] = DrawRec{d.first_index, d.triangle_count, d.vertex_offset, d.first_vertex, d.vertex_count, d.transform,
+                          d.material, slot_base, triangle_base};
+        slot_base += d.vertex_count;
+        triangle_base += d.triangle_count;
+    }
+    hipStream_t s = hs(stream);
+    uint32_t failed = DRAWS_OK;
+    // recs and failed live on this frame's stack: the stream is synchronised before it returns
+    bool ok = hipMemsetAsync(dw.flag, 0xFF, 256, s) == hipSuccess;
+    if (ok && D > 0) ok = hipMemcpyAsync(dw.draws, recs.data(), (size_t)D * sizeof(DrawRec), hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok && S > 0)
+        launch("draws_build_slots", kWorkgroup, draws_build_slots, ceil_div(S, 256), kWorkgroup, 0, s, scene->uvs, dw, D, S);
+    if (ok && T > 0)
+        launch("draws_build_tris", kWorkgroup, draws_build_tris, ceil_div(T, 256), kWorkgroup, 0, s, scene->indices, dw, D, T);
+    if (ok) rc = check_launch("soc_draw_scene_build");
+    if (ok && !rc) ok = hipMemcpyAsync(&failed, dw.flag, sizeof failed, hipMemcpyDeviceToHost, s) == hipSuccess;
+    const bool synced = hipStreamSynchronize(s) == hipSuccess;
+    if (rc) return rc;
+    if (!ok || !synced) {
+        (void)hipGetLastError();
+        return set_error(SOC_E_HIP, "soc_draw_scene_build: copying the draw tables or reading the validation flag failed");
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_draws_mutex);
+        g_draws_built[scene->workspace] = DrawBuilt{draw_fingerprint(scene), failed};
+    }
+    if (failed != DRAWS_OK) {
+        const soc_draw& d = scene->draws[failed];
+        return set_error(SOC_E_SHAPE, "soc_draw_scene_build: draw %u fetches an index that, with vertex_offset %d, lies outside "
+                         "its vertex range [%d, %d)", failed, d.vertex_offset, d.first_vertex, d.first_vertex + d.vertex_count);
+    }
+    return SOC_OK;
+}
+
+extern "C" int soc_raster_visibility_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                           uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
+                                           soc_stream stream) {
+    DrawTotals tot;
+    int rc = check_built_scene(scene, "soc_raster_visibility_draws", false, tot);
+    if (rc) return rc;
+    if (!view_projection || !visibility || width <= 0 || height <= 0 || cull < 0 || cull > 2)
+        return set_error(SOC_E_INVALID_ARG, "soc_raster_visibility_draws: null argument, bad extent or cull mode");
+    hipStream_t s = hs(stream);
+    if (clear) {
+        const size_t n = (size_t)width * height;
+        launch("raster_clear_vis", kWorkgroup, raster_clear_vis, (unsigned)((n + 255) / 256), kWorkgroup, 0, s, reinterpret_cast<unsigned long long*>(visibility), n);
+    }
+    RasterParams p{};
+    p.vp = mat4(view_projection);
+    p.width = width;
+    p.height = height;
+    p.cull = cull;
+    p.small_pixels = SMALL_PIXELS;
+    return launch_raster_draws(scene, tot, 0, p, visibility, (size_t)width * 8, s, "raster_visibility_draws");
+}
+
+extern "C" int soc_raster_depth_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                      float bias_constant, float bias_slope, soc_img depth, soc_stream stream) {
+    DrawTotals tot;
+    int rc = check_built_scene(scene, "soc_raster_depth_draws", false, tot);
+    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "soc_raster_depth_draws", "depth");
+    if (rc) return rc;
+    if (!view_projection || cull < 0 || cull > 2)
+        return set_error(SOC_E_INVALID_ARG, "soc_raster_depth_draws: null argument or bad cull mode");
+    hipStream_t s = hs(stream);
+    launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)), kWorkgroup, 0, s,
+           static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
+    RasterParams p{};
+    p.vp = mat4(view_projection);
+    p.width = depth.width;
+    p.height = depth.height;
+    p.cull = cull;
+    p.small_pixels = SMALL_PIXELS;
+    p.depth_only = 1;
+    p.bias_constant = bias_constant;
+    p.bias_slope = bias_slope;
+    return launch_raster_draws(scene, tot, 1, p, depth.data, (size_t)depth.pitch_bytes, s, "raster_depth_draws");
+}
+
+extern "C" int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene, const soc_material* d_materials,
+                                         int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
+                                         soc_img emissive, soc_img normal, soc_img velocity, soc_stream stream) {
+    DrawTotals tot;
+    int rc = check_built_scene(scene, "soc_gbuffer_resolve_draws", true, tot);
+    if (rc) return rc;
+    ResolveParams p{};
+    dim3 blk(64, 4), grd;
+    rc = resolve_prepare("soc_gbuffer_resolve_draws", g, d_materials, material_count, visibility, depth, albedo, emissive,
+                         normal, velocity, p, grd);
+    if (rc) return rc;
+    if (material_count < scene->material_count)
+        return set_error(SOC_E_SHAPE, "soc_gbuffer_resolve_draws: %d materials, the scene's draws name up to %d", material_count,
+                         scene->material_count);
+    const int S = (int)tot.slots, T = (int)tot.triangles;
+    p.triangle_count = T;
+    const DrawWorkspace dw = draw_carve(scene->workspace, tot.slots, tot.triangles, scene->draw_count);
+    const Workspace ws = carve(dw.view[0], S, T);
+    // the scene's vertex arrays for the vertex stage; the tables as one mesh for the resolve (it reads the indices, the
+    // uvs by slot, the materials and the per-slot vertex data only)
+    soc_mesh src{};
+    src.positions = scene->positions;
+    src.normals = scene->normals;
+    src.vertex_count = scene->vertex_count;
+    soc_mesh view{};
+    view.uvs = reinterpret_cast<const float*>(dw.slot_uvs);
+    view.indices = dw.indices;
+    view.materials = dw.materials;
+    view.vertex_count = S;
+    view.triangle_count = T;
+    hipStream_t s = hs(stream);
+    if (S > 0)
+        launch("gbuffer_vertex_setup_draws", kWorkgroup, gbuffer_vertex_setup_draws, ceil_div(S, 256), kWorkgroup, 0, s, src, dw.slots,
+               scene->transforms, S, ws.vdata, p);
+    launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true>, grd, blk, 0, s, view, d_materials,
+           reinterpret_cast<const unsigned long long*>(visibility), dimg(depth), dimg(albedo), dimg(emissive), dimg(normal),
+           dimg(velocity), ws.vdata, p);
+    return check_launch("gbuffer_resolve_draws");
 }

@@ -22,7 +22,8 @@ from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, FMT_RGBA8_SRGB, FMT_RGBA8_U
 
 __all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "MATERIAL_ZERO_VELOCITY", "MeshBuffers", "MipTexture", "material",
            "normal_matrix", "materials_device", "raster_visibility", "raster_depth", "gbuffer_resolve",
-           "SHADOW_BIAS_CONSTANT", "SHADOW_BIAS_SLOPE"]
+           "SHADOW_BIAS_CONSTANT", "SHADOW_BIAS_SLOPE", "DrawScene", "draw", "transforms_device", "update_transforms",
+           "raster_visibility_draws", "raster_depth_draws", "gbuffer_resolve_draws"]
 
 # sun_shadow_draw.inl:47-50 / :81
 SHADOW_BIAS_CONSTANT = 1.25
@@ -222,6 +223,111 @@ def gbuffer_resolve(g, mesh: MeshBuffers, d_materials: torch.Tensor, material_co
     _check(lib().soc_gbuffer_resolve(_gp(g), C.byref(mesh.struct), _ptr(d_materials), int(material_count),
                                      _ptr(visibility), img(depth), img(albedo), img(emissive), img(normal), img(velocity),
                                      _ptr(workspace), _stream(stream)), "gbuffer_resolve")
+
+
+# ------------------------------------------------------------------------------------------------
+# draw scenes: per-entity draws with their own transforms (include/soc_rt.h "Draw scenes")
+# ------------------------------------------------------------------------------------------------
+def draw(first_index: int, triangle_count: int, first_vertex: int, vertex_count: int, transform: int = 0,
+         material: int = 0, vertex_offset: int = 0) -> _abi.Draw:
+    """soc_draw: one draw_indexed {3 triangle_count, first_index, vertex_offset} of one entity; the offset indices
+    must fall in [first_vertex, first_vertex + vertex_count)."""
+    return _abi.Draw(int(first_index), int(triangle_count), int(vertex_offset), int(first_vertex), int(vertex_count),
+                     int(transform), int(material))
+
+
+def _transform_rows(model_matrices, normal_matrices) -> np.ndarray:
+    m = np.asarray(model_matrices, np.float32).reshape(-1, 16)
+    n = np.asarray(normal_matrices, np.float32).reshape(-1, 16)
+    if m.shape != n.shape:
+        raise ValueError("one normal matrix per model matrix")
+    return np.ascontiguousarray(np.concatenate([m, n], axis=1))
+
+
+def transforms_device(model_matrices, normal_matrices, device="cuda") -> torch.Tensor:
+    """Device soc_transform array, (N, 32) float32, from soc.scene_update's outputs ((N, 4, 4) model and normal
+    matrices, row index = glm column: the column-major layout the struct holds)."""
+    return torch.from_numpy(_transform_rows(model_matrices, normal_matrices)).to(device)
+
+
+def update_transforms(transforms: torch.Tensor, model_matrices, normal_matrices, first: int = 0) -> None:
+    """Rewrites transforms[first : first + N] in place on the current stream (the next frame's matrices; no rebuild)."""
+    rows = _transform_rows(model_matrices, normal_matrices)
+    transforms[first:first + rows.shape[0]].copy_(torch.from_numpy(rows))
+
+
+class DrawScene:
+    """soc_draw_scene: shared vertex / index arrays (torch device tensors, or numpy arrays uploaded to `device`), a list
+    of draws (draw(...)), the device transform array (transforms_device) and the material count the draws index. Owns
+    the workspace and, with build=True, runs soc_draw_scene_build (raises SocError naming the draw when an index lies
+    outside its draw's vertex range)."""
+
+    def __init__(self, positions, normals, uvs, indices, draws, transforms: torch.Tensor, material_count: int = 1,
+                 device="cuda", build: bool = True, stream=None):
+        def dev(a, dt):
+            if a is None or isinstance(a, torch.Tensor):
+                return a
+            return torch.from_numpy(np.ascontiguousarray(a, dt)).to(device)
+        self.positions, self.normals, self.uvs = dev(positions, np.float32), dev(normals, np.float32), dev(uvs, np.float32)
+        self.indices = dev(indices if isinstance(indices, torch.Tensor) else np.asarray(indices).reshape(-1), np.uint32)
+        self.transforms = transforms
+        self.draws = list(draws)
+        self._draw_array = (_abi.Draw * max(len(self.draws), 1))(*self.draws)
+        n = int(lib().soc_draw_workspace_size(self._draw_array, len(self.draws)))
+        if n == 0:
+            raise ValueError("bad draw list (negative field, or too many triangles / vertices)")
+        self.workspace = torch.empty(n, dtype=torch.uint8, device=self.positions.device)
+        s = _abi.DrawSceneStruct()
+        s.positions, s.normals, s.uvs, s.indices = _ptr(self.positions), _ptr(self.normals), _ptr(self.uvs), _ptr(self.indices)
+        s.vertex_count = int(self.positions.shape[0])
+        s.index_count = int(self.indices.numel())
+        s.draws = self._draw_array
+        s.draw_count = len(self.draws)
+        s.transforms = _ptr(transforms)
+        s.transform_count = int(transforms.shape[0])
+        s.material_count = int(material_count)
+        s.workspace = _ptr(self.workspace)
+        self.struct = s
+        if build:
+            self.build(stream)
+
+    def build(self, stream=None) -> None:
+        _check(lib().soc_draw_scene_build(C.byref(self.struct), _stream(stream)), "draw_scene_build")
+
+    def close(self) -> None:
+        """Forgets the build record of the workspace (before it is freed)."""
+        if getattr(self, "struct", None) is not None:
+            lib().soc_draw_scene_release(C.byref(self.struct))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def raster_visibility_draws(scene: DrawScene, view_projection, cull, visibility: torch.Tensor, clear=True, stream=None):
+    """raster_visibility of a draw scene: global triangle ids in draw order."""
+    H, W = visibility.shape
+    vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    _check(lib().soc_raster_visibility_draws(C.byref(scene.struct), vp, int(cull), _ptr(visibility), W, H, int(bool(clear)),
+                                             _stream(stream)), "raster_visibility_draws")
+
+
+def raster_depth_draws(scene: DrawScene, view_projection, cull, depth: torch.Tensor, bias_constant=0.0, bias_slope=0.0,
+                       stream=None):
+    """raster_depth of a draw scene (the sun shadow map with SHADOW_BIAS_*)."""
+    vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    _check(lib().soc_raster_depth_draws(C.byref(scene.struct), vp, int(cull), float(bias_constant), float(bias_slope),
+                                        img(depth), _stream(stream)), "raster_depth_draws")
+
+
+def gbuffer_resolve_draws(g, scene: DrawScene, d_materials: torch.Tensor, material_count: int, visibility: torch.Tensor,
+                          depth, albedo, emissive, normal, velocity, stream=None):
+    """gbuffer_resolve of a draw scene's visibility buffer (always through the per-vertex workspace)."""
+    _check(lib().soc_gbuffer_resolve_draws(_gp(g), C.byref(scene.struct), _ptr(d_materials), int(material_count),
+                                           _ptr(visibility), img(depth), img(albedo), img(emissive), img(normal),
+                                           img(velocity), _stream(stream)), "gbuffer_resolve_draws")
 
 
 def visibility_triangles(vis) -> np.ndarray:
