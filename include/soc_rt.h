@@ -778,7 +778,8 @@ int soc_renderer_set_raster_scene(soc_renderer* r, const soc_raster_scene* scene
  * draw, and within a draw the later triangle, wins (LESS_OR_EQUAL in draw order). Every vertex of a draw goes through
  * the single-mesh vertex arithmetic with that draw's matrices (the same bits as a soc_mesh holding the draw). Culling,
  * depth clipping, bias and clear values are unchanged. Velocity follows the reference: the previous clip position uses
- * the CURRENT model matrix (g_buffer_generation.inl:171); per-object motion vectors are out of scope. */
+ * the CURRENT model matrix (g_buffer_generation.inl:171); per-object motion vectors from the previous frame's
+ * transforms are opt-in ("Draw scenes: per-object motion vectors" below). */
 typedef struct soc_transform {         /* TransformComponent buffer; what soc_scene_update writes per entity */
     float model_matrix[16];            /* column-major */
     float normal_matrix[16];           /* its upper 3x3 transforms normals */
@@ -848,6 +849,35 @@ int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene,
  * also under SOC_RENDERER_STATIC_INPUTS (see there). */
 int soc_renderer_set_draw_scene(soc_renderer* r, const soc_draw_scene* scene, const soc_material* d_materials,
                                 int32_t material_count, int32_t shadow, uint64_t* visibility);
+
+/* --- Draw scenes: per-object motion vectors (opt-in) ----------------------------
+ * The reference forms the previous clip position with the CURRENT model matrix, so the velocity of an entity that moved
+ * holds the camera's motion only and TAA reprojects it from where it never was. soc_gbuffer_resolve_draws_motion is
+ * soc_gbuffer_resolve_draws with one more device array, the transforms of the PREVIOUS frame (same index, same
+ * transform_count entries as scene->transforms; only each model_matrix is read): the previous clip position of a vertex
+ * of draw d becomes previous_vp . (previous[d.transform].model_matrix . p), the current-frame chain's operations in its
+ * order. Everything else (depth, albedo, emissive, normal, the current clip position) is computed as before. A draw
+ * whose previous model matrix equals its current one bit for bit gets the bits of soc_gbuffer_resolve_draws, and
+ * previous_transforms == scene->transforms (the arrays may alias) reproduces that call entirely. The same host-side
+ * checks and refusals of an unbuilt, changed or failed workspace, all before any HIP call; a NULL previous_transforms
+ * is SOC_E_INVALID_ARG. */
+int soc_gbuffer_resolve_draws_motion(const soc_globals* g, const soc_draw_scene* scene,
+                                     const soc_transform* previous_transforms, const soc_material* d_materials,
+                                     int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
+                                     soc_img emissive, soc_img normal, soc_img velocity, soc_stream stream);
+/* The render graph's GBufferGeneration with per-object motion. `previous_transforms` is CALLER memory like the
+ * transforms (device, the draw scene's transform_count entries) that the RENDERER writes: GBufferGeneration calls the
+ * motion resolve with it and then copies the current transforms into it for the next frame, on the caller's stream
+ * inside the same pass (after the resolve's vertex stage, so before the caller's next rewrite of the transforms by
+ * stream order; nothing is allocated, no pass is added: names, groups, declared uses and lanes stay as they are). The
+ * first frame after this call copies current -> previous before the vertex stage too, so it gives the reference's
+ * velocity. NULL turns motion off. SOC_E_INVALID_ARG when no draw scene is set. soc_renderer_set_draw_scene and
+ * soc_renderer_set_raster_scene (with a scene or NULL) turn motion off again: a new scene may have another transform
+ * count. The history array is not renderer state: it is not part of the Python Renderer's save_state / load_state. A
+ * caller who wants continuity after load_state restores the array's contents itself (the transforms of the frame
+ * before the checkpoint) in a renderer whose motion is on and has run a frame; this call itself always restarts the
+ * history, so the frame after it has the reference's velocity. */
+int soc_renderer_set_draw_motion(soc_renderer* r, soc_transform* previous_transforms);
 
 /* --- Headless output and metrics (replaces the swapchain present of tone_mapping.inl:
  * 172-176 and the ImGui "GPU Metric" window of renderer.cpp:769-806) ------------------------------- */

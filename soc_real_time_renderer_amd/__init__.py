@@ -470,7 +470,7 @@ class Renderer:
         arrays; None clears it (the G-buffer images are inputs again)."""
         if mesh is None:
             _check(lib().soc_renderer_set_raster_scene(self.handle, None), "soc_renderer_set_raster_scene")
-            self._scene = None
+            self._scene = self._motion = None
             return
         sc = _abi.RasterScene()
         sc.mesh = mesh.struct
@@ -481,18 +481,31 @@ class Renderer:
         sc.workspace = _ptr(workspace)
         self._scene = (mesh, d_materials, visibility, workspace)   # keep the arrays alive
         _check(lib().soc_renderer_set_raster_scene(self.handle, C.byref(sc)), "soc_renderer_set_raster_scene")
+        self._motion = None   # a new scene turns a draw scene's per-object motion off
 
-    def set_draw_scene(self, scene, d_materials, material_count: int, visibility, shadow: bool = True):
+    def set_draw_scene(self, scene, d_materials, material_count: int, visibility, shadow: bool = True, motion=None):
         """Raster head from a raster.DrawScene (per-entity draws with their own transforms); replaces a
         set_raster_scene scene and the other way round; None clears. The renderer keeps the device pointer to
-        scene.transforms: rewrite it in place (raster.update_transforms) between frames."""
+        scene.transforms: rewrite it in place (raster.update_transforms) between frames. Setting a scene turns
+        per-object motion off; `motion` (a history tensor, see set_draw_motion) turns it on for the new scene."""
         if scene is None:
             _check(lib().soc_renderer_set_draw_scene(self.handle, None, None, 0, 0, None), "soc_renderer_set_draw_scene")
-            self._scene = None
+            self._scene = self._motion = None
             return
         self._scene = (scene, d_materials, visibility)   # keep the arrays alive
         _check(lib().soc_renderer_set_draw_scene(self.handle, C.byref(scene.struct), _ptr(d_materials), int(material_count),
                                                  int(bool(shadow)), _ptr(visibility)), "soc_renderer_set_draw_scene")
+        self._motion = None
+        if motion is not None:
+            self.set_draw_motion(motion)
+
+    def set_draw_motion(self, previous_transforms):
+        """Per-object motion vectors for the draw scene: `previous_transforms` is a device tensor shaped like
+        scene.transforms that the renderer keeps as last frame's transforms (GBufferGeneration reads it, then copies
+        the current transforms into it on the caller's stream); the first frame after the call has the reference's
+        velocity. None turns motion off. The tensor is the caller's: it is not part of save_state / load_state."""
+        _check(lib().soc_renderer_set_draw_motion(self.handle, _ptr(previous_transforms)), "soc_renderer_set_draw_motion")
+        self._motion = previous_transforms   # keep the array alive
 
     def metrics_json(self, frame: int = 0) -> str:
         """The last frame's GPU-metric record (renderer.cpp:769-806) as a JSON string (needs timing and a

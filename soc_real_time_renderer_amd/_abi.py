@@ -303,11 +303,15 @@ FUNCTIONS = {
     "soc_gbuffer_resolve_draws": (_I, [_G, C.POINTER(DrawSceneStruct), _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG, _IMG,
                                        _P]),
     "soc_renderer_set_draw_scene": (_I, [_P, C.POINTER(DrawSceneStruct), _P, C.c_int32, C.c_int32, _P]),
+    "soc_gbuffer_resolve_draws_motion": (_I, [_G, C.POINTER(DrawSceneStruct), _P, _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG,
+                                              _IMG, _P]),
+    "soc_renderer_set_draw_motion": (_I, [_P, _P]),
 }
 
 # not in the public header: test hooks
 DEBUG_FUNCTIONS = {
     "soc_debug_bloom_generic": (_I, [C.c_int32, _IMG, _IMG, _P]),
+    "soc_debug_draw_motion": (_I, [_P]),
 }
 
 

@@ -672,6 +672,11 @@ struct soc_renderer {
     soc_draw_scene draw_scene{};
     std::vector<soc_draw> draws;
     bool has_draws = false;
+    // soc_renderer_set_draw_motion: the caller's history array (draw_scene.transform_count entries, device) the motion
+    // resolve reads as last frame's transforms and GBufferGeneration rewrites every frame; null = motion off.
+    // motion_valid: the array holds the transforms of the previous GBufferGeneration (false until the first one).
+    soc_transform* motion_prev = nullptr;
+    bool motion_valid = false;
     std::vector<Pass> passes;
     std::vector<UserPass> user_passes;
     uint32_t flags = 0;
@@ -821,6 +826,28 @@ void build_raster_passes(soc_renderer* r) {
              res_mask({SOC_RES_ALBEDO, SOC_RES_EMISSIVE, SOC_RES_NORMAL, SOC_RES_VELOCITY, SOC_RES_DEPTH}),
              [r](const soc_globals* g, hipStream_t s) {
                  const soc_frame_images& I = r->img;
+                 if (r->has_draws && r->motion_prev) {
+                     // per-object motion vectors: the history array is kept here, on the caller's stream. A history that
+                     // holds no frame yet is first made equal to the current transforms (the reference's velocity); after
+                     // the resolve's vertex stage the current transforms become the next frame's history, ahead of the
+                     // caller's next rewrite of them by stream order.
+                     const soc_draw_scene& sc = r->draw_scene;
+                     const size_t bytes = (size_t)sc.transform_count * sizeof(soc_transform);
+                     const bool own = r->motion_prev != sc.transforms;   // the transforms as their own history: no copies
+                     if (!r->motion_valid) {
+                         if (own && hipMemcpyAsync(r->motion_prev, sc.transforms, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                             return set_error(SOC_E_HIP, "GBufferGeneration: initialising the motion history failed");
+                         r->motion_valid = true;
+                     }
+                     const int rc = soc_gbuffer_resolve_draws_motion(g, &sc, r->motion_prev, r->scene.materials,
+                                                                     r->scene.material_count, r->scene.visibility, I.depth,
+                                                                     I.albedo, I.emissive, I.normal, frame_velocity(r),
+                                                                     (soc_stream)s);
+                     if (rc) return rc;
+                     if (own && hipMemcpyAsync(r->motion_prev, sc.transforms, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                         return set_error(SOC_E_HIP, "GBufferGeneration: updating the motion history failed");
+                     return SOC_OK;
+                 }
                  if (r->has_draws)
                      return soc_gbuffer_resolve_draws(g, &r->draw_scene, r->scene.materials, r->scene.material_count,
                                                       r->scene.visibility, I.depth, I.albedo, I.emissive, I.normal,
@@ -1638,6 +1665,8 @@ extern "C" int soc_renderer_set_raster_scene(soc_renderer* r, const soc_raster_s
     r->has_scene = scene != nullptr;
     r->has_draws = false;
     r->draws.clear();
+    r->motion_prev = nullptr;   // a new scene turns per-object motion off (soc_renderer_set_draw_motion)
+    r->motion_valid = false;
     if (scene) r->scene = *scene;
     int rc = build_graph(r);
     if (rc) return rc;
@@ -1669,11 +1698,25 @@ extern "C" int soc_renderer_set_draw_scene(soc_renderer* r, const soc_draw_scene
     r->scene.shadow = shadow != 0;
     r->scene.visibility = visibility;
     r->has_scene = r->has_draws = true;
+    r->motion_prev = nullptr;   // the new scene may have another transform count: motion is set again after it
+    r->motion_valid = false;
     int rc = build_graph(r);
     if (rc) return rc;
     if (r->flags & SOC_RENDERER_TIMING) return soc_renderer_set_pass_timing(r, -1, 1);
     return SOC_OK;
 }
+
+extern "C" int soc_renderer_set_draw_motion(soc_renderer* r, soc_transform* previous_transforms) {
+    if (!r) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_draw_motion: null renderer");
+    if (!r->has_draws) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_draw_motion: no draw scene is set");
+    // the graph is not rebuilt: GBufferGeneration looks at motion_prev when it runs
+    r->motion_prev = previous_transforms;
+    r->motion_valid = false;
+    return SOC_OK;
+}
+
+// Test hook (not in the public header): 1 when per-object motion is on, so its switching can be checked without a GPU.
+extern "C" int soc_debug_draw_motion(const soc_renderer* r) { return r && r->has_draws && r->motion_prev ? 1 : 0; }
 
 // Registers `up` (its callback, or a library-owned pass's images, already set) under the descriptor `d`: the
 // descriptor checks, the rebuild and the roll-back shared by soc_renderer_add_pass and the library-owned passes.

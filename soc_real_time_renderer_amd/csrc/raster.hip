@@ -761,6 +761,21 @@ __device__ __forceinline__ VtxData vertex_data(const soc_mesh& mesh, uint32_t v,
     return d;
 }
 
+// vertex_data with per-object motion (draw scenes): the previous clip position from the draw's model
+// matrix of the PREVIOUS frame, prev_vp . (prev_model . p), the current chain's operations in its order; everything else
+// is vertex_data's (pc.w stays the current world z). A prev_model equal to p.model bit for bit gives vertex_data's bits:
+// the same operations on the same operands.
+__device__ __forceinline__ VtxData vertex_data_motion(const soc_mesh& mesh, uint32_t v, const ResolveParams& p,
+                                                      const Mat4& prev_model) {
+#pragma clang fp contract(off)
+    VtxData d = vertex_data(mesh, v, p);
+    const float* ps = mesh.positions;
+    const f4 wq = mat_vec_exact(prev_model, ps[3 * v], ps[3 * v + 1], ps[3 * v + 2], 1.0f);
+    const f4 q = mat_vec_exact(p.prev_vp, wq.x, wq.y, wq.z, wq.w);
+    d.pc = float4{q.x, q.y, q.w, d.pc.w};
+    return d;
+}
+
 __global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup(soc_mesh mesh, float4* __restrict__ vd, ResolveParams p) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= mesh.vertex_count) return;
@@ -978,7 +993,9 @@ int launch_raster(const soc_mesh* mesh, const RasterParams& p, void* target, siz
 //                                 vertex_offset against the draw's vertex range, rebases them to the draw's slots and
 //                                 writes the triangle's material
 //   per frame  raster_setup_draws / gbuffer_vertex_setup_draws: raster_setup / gbuffer_vertex_setup per slot, with the
-//                                 slot's source vertex and its draw's matrices (clip_vertex / vertex_data as they are)
+//                                 slot's source vertex and its draw's matrices (clip_vertex / vertex_data as they are);
+//                                 gbuffer_vertex_setup_draws_motion: the same with the previous clip position from the
+//                                 draw's model matrix of the previous frame (opt-in per-object motion vectors)
 // raster_small, raster_big and gbuffer_resolve<true> then run UNCHANGED on a single-mesh view of the tables (slot count
 // as the vertex count, the rebased indices, the slot uvs, the per-triangle materials): a triangle's global id is its
 // position in the rebased index buffer, so the keys and the tie rule are the serial draw loop's.
@@ -1159,6 +1176,60 @@ __global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup_draws(soc_mes
         const float* nm = t.normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
         q.normal3 = Mat3{{nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]}};
         const VtxData d = vertex_data(mesh, sl.x, q);
+        if (!live) return;
+        vd[4 * i] = d.s;
+        vd[4 * i + 1] = d.n;
+        vd[4 * i + 2] = d.cc;
+        vd[4 * i + 3] = d.pc;
+    });
+}
+
+// The motion form of with_slot_transform (soc_gbuffer_resolve_draws_motion): f gets the slot's current transform and its
+// draw's PREVIOUS model matrix (prev[t].model_matrix; the previous normal matrix is never read). A wave inside one draw
+// fetches both in one load instruction, lanes 0-31 the current record's 32 floats and lanes 32-47 the previous model
+// matrix's 16, into its LDS record (192 bytes per wave); a wave that straddles draws loads per lane. xf and prev may
+// be the same array. The same rule: every lane of the workgroup calls this, once per kernel.
+struct MotionXf {
+    soc_transform cur;
+    float prev_model[16];
+};
+template <typename F>
+__device__ __forceinline__ void with_slot_transform_motion(const soc_transform* xf, const soc_transform* prev, uint32_t t,
+                                                           F&& f) {
+#if !SOC_DRAWS_LDS_TRANSFORM
+    f(xf[t], prev[t].model_matrix);
+#else
+    static_assert(sizeof(MotionXf) == 48 * sizeof(float), "one float per lane of three quarters of a wave");
+    __shared__ MotionXf wave_xf[kWorkgroup / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t first = __builtin_amdgcn_readfirstlane(t);
+    const bool uniform = __all(t == first);
+    if (uniform && lane < 48) {
+        const float* src = lane < 32 ? reinterpret_cast<const float*>(&xf[first]) + lane : prev[first].model_matrix + (lane - 32);
+        reinterpret_cast<float*>(&wave_xf[wave])[lane] = *src;
+    }
+    __syncthreads();
+    if (uniform) f(wave_xf[wave].cur, wave_xf[wave].prev_model);
+    else f(xf[t], prev[t].model_matrix);
+#endif
+}
+
+// gbuffer_vertex_setup_draws with per-object motion: everything but pc as there (the same vertex_data, the same current
+// matrices); pc from the draw's previous model matrix, its .w payload still the current world z.
+__global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup_draws_motion(soc_mesh mesh, const uint2* __restrict__ slots,
+                                                                         const soc_transform* xf, const soc_transform* prev,
+                                                                         int slot_count, float4* __restrict__ vd,
+                                                                         ResolveParams p) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (slot_count == 0) return;
+    const bool live = i < slot_count;
+    const uint2 sl = slots[live ? i : slot_count - 1];
+    with_slot_transform_motion(xf, prev, sl.y, [&](const soc_transform& t, const float* prev_model) {
+        ResolveParams q = p;
+        q.model = mat4_of(t.model_matrix);
+        const float* nm = t.normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
+        q.normal3 = Mat3{{nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]}};
+        const VtxData d = vertex_data_motion(mesh, sl.x, q, mat4_of(prev_model));
         if (!live) return;
         vd[4 * i] = d.s;
         vd[4 * i + 1] = d.n;
@@ -1480,19 +1551,21 @@ extern "C" int soc_raster_depth_draws(const soc_draw_scene* scene, const float v
     return launch_raster_draws(scene, tot, 1, p, depth.data, (size_t)depth.pitch_bytes, s, "raster_depth_draws");
 }
 
-extern "C" int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene, const soc_material* d_materials,
-                                         int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
-                                         soc_img emissive, soc_img normal, soc_img velocity, soc_stream stream) {
+// soc_gbuffer_resolve_draws (previous null) and soc_gbuffer_resolve_draws_motion: the same checks, tables and resolve; the
+// vertex stage is gbuffer_vertex_setup_draws or its motion form.
+static int resolve_draws(const char* name, const char* pass, const soc_globals* g, const soc_draw_scene* scene,
+                         const soc_transform* previous, const soc_material* d_materials, int32_t material_count,
+                         const uint64_t* visibility, const soc_img& depth, const soc_img& albedo, const soc_img& emissive,
+                         const soc_img& normal, const soc_img& velocity, soc_stream stream) {
     DrawTotals tot;
-    int rc = check_built_scene(scene, "soc_gbuffer_resolve_draws", true, tot);
+    int rc = check_built_scene(scene, name, true, tot);
     if (rc) return rc;
     ResolveParams p{};
     dim3 blk(64, 4), grd;
-    rc = resolve_prepare("soc_gbuffer_resolve_draws", g, d_materials, material_count, visibility, depth, albedo, emissive,
-                         normal, velocity, p, grd);
+    rc = resolve_prepare(name, g, d_materials, material_count, visibility, depth, albedo, emissive, normal, velocity, p, grd);
     if (rc) return rc;
     if (material_count < scene->material_count)
-        return set_error(SOC_E_SHAPE, "soc_gbuffer_resolve_draws: %d materials, the scene's draws name up to %d", material_count,
+        return set_error(SOC_E_SHAPE, "%s: %d materials, the scene's draws name up to %d", name, material_count,
                          scene->material_count);
     const int S = (int)tot.slots, T = (int)tot.triangles;
     p.triangle_count = T;
@@ -1511,11 +1584,32 @@ extern "C" int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_sc
     view.vertex_count = S;
     view.triangle_count = T;
     hipStream_t s = hs(stream);
-    if (S > 0)
+    if (S > 0 && previous)
+        launch("gbuffer_vertex_setup_draws_motion", kWorkgroup, gbuffer_vertex_setup_draws_motion, ceil_div(S, 256), kWorkgroup, 0,
+               s, src, dw.slots, scene->transforms, previous, S, ws.vdata, p);
+    else if (S > 0)
         launch("gbuffer_vertex_setup_draws", kWorkgroup, gbuffer_vertex_setup_draws, ceil_div(S, 256), kWorkgroup, 0, s, src, dw.slots,
                scene->transforms, S, ws.vdata, p);
     launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true>, grd, blk, 0, s, view, d_materials,
            reinterpret_cast<const unsigned long long*>(visibility), dimg(depth), dimg(albedo), dimg(emissive), dimg(normal),
            dimg(velocity), ws.vdata, p);
-    return check_launch("gbuffer_resolve_draws");
+    return check_launch(pass);
+}
+
+extern "C" int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene, const soc_material* d_materials,
+                                         int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
+                                         soc_img emissive, soc_img normal, soc_img velocity, soc_stream stream) {
+    return resolve_draws("soc_gbuffer_resolve_draws", "gbuffer_resolve_draws", g, scene, nullptr, d_materials, material_count,
+                         visibility, depth, albedo, emissive, normal, velocity, stream);
+}
+
+extern "C" int soc_gbuffer_resolve_draws_motion(const soc_globals* g, const soc_draw_scene* scene,
+                                                const soc_transform* previous_transforms, const soc_material* d_materials,
+                                                int32_t material_count, const uint64_t* visibility, soc_img depth,
+                                                soc_img albedo, soc_img emissive, soc_img normal, soc_img velocity,
+                                                soc_stream stream) {
+    if (!previous_transforms)
+        return set_error(SOC_E_INVALID_ARG, "soc_gbuffer_resolve_draws_motion: null previous_transforms");
+    return resolve_draws("soc_gbuffer_resolve_draws_motion", "gbuffer_resolve_draws_motion", g, scene, previous_transforms,
+                         d_materials, material_count, visibility, depth, albedo, emissive, normal, velocity, stream);
 }

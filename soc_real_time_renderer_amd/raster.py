@@ -23,7 +23,8 @@ from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, FMT_RGBA8_SRGB, FMT_RGBA8_U
 __all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "MATERIAL_ZERO_VELOCITY", "MeshBuffers", "MipTexture", "material",
            "normal_matrix", "materials_device", "raster_visibility", "raster_depth", "gbuffer_resolve",
            "SHADOW_BIAS_CONSTANT", "SHADOW_BIAS_SLOPE", "DrawScene", "draw", "transforms_device", "update_transforms",
-           "raster_visibility_draws", "raster_depth_draws", "gbuffer_resolve_draws"]
+           "raster_visibility_draws", "raster_depth_draws", "gbuffer_resolve_draws",
+           "gbuffer_resolve_draws_motion"]
 
 # sun_shadow_draw.inl:47-50 / :81
 SHADOW_BIAS_CONSTANT = 1.25
@@ -328,6 +329,18 @@ def gbuffer_resolve_draws(g, scene: DrawScene, d_materials: torch.Tensor, materi
     _check(lib().soc_gbuffer_resolve_draws(_gp(g), C.byref(scene.struct), _ptr(d_materials), int(material_count),
                                            _ptr(visibility), img(depth), img(albedo), img(emissive), img(normal),
                                            img(velocity), _stream(stream)), "gbuffer_resolve_draws")
+
+
+def gbuffer_resolve_draws_motion(g, scene: DrawScene, previous_transforms: torch.Tensor, d_materials: torch.Tensor,
+                                 material_count: int, visibility: torch.Tensor, depth, albedo, emissive, normal, velocity,
+                                 stream=None):
+    """gbuffer_resolve_draws with per-object motion vectors: the previous clip position of every draw comes from
+    previous_transforms (device, (N, 32) float32 like scene.transforms: last frame's array; it may be scene.transforms
+    itself, which gives gbuffer_resolve_draws' bits). Everything but the velocity is gbuffer_resolve_draws'."""
+    _check(lib().soc_gbuffer_resolve_draws_motion(_gp(g), C.byref(scene.struct), _ptr(previous_transforms),
+                                                  _ptr(d_materials), int(material_count), _ptr(visibility), img(depth),
+                                                  img(albedo), img(emissive), img(normal), img(velocity), _stream(stream)),
+           "gbuffer_resolve_draws_motion")
 
 
 def visibility_triangles(vis) -> np.ndarray:

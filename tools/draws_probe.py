@@ -4,9 +4,12 @@
   mesh       through the single-mesh entry points (the baseline, same build);
   one_draw   as a draw scene of one draw;
   per_material  as one draw per material (25 draws, triangles sorted by material), each with its own transform;
+  per_material_motion  the per_material scene resolved with per-object motion vectors (soc_gbuffer_resolve_draws_motion),
+                its previous-transform array a separate copy equal to the current one (the resolve rows only: the
+                visibility and shadow calls do not differ);
 
-every transform holding the same (identity) matrix, so the three visibility buffers, shadow maps and G-buffers must be
-torch.equal: the probe asserts that before it times anything. Timed with device events around `--launches` calls,
+every transform holding the same (identity) matrix, so the three visibility buffers, shadow maps and G-buffers (and the
+motion resolve's G-buffer) must be torch.equal: the probe asserts that before it times anything. Timed with device events around `--launches` calls,
 `--rounds` times (the spread), after a warm-up of the same calls:
 
   vertex_setup_us   the raster's vertex stage alone: the call on a twin of the scene with the same vertices / slots and
@@ -111,7 +114,8 @@ def main():
 
     def gb(o):
         return o["depth"], o["albedo"], o["emissive"], o["normal"], o["velocity"]
-    out = {n: images() for n in ("mesh", "one_draw", "per_material")}
+    out = {n: images() for n in ("mesh", "one_draw", "per_material", "per_material_motion")}
+    previous = forms["per_material"].transforms.clone()          # previous == current, in memory of its own
     empty_vis = torch.zeros((H, W), dtype=torch.int64, device=dev)
     raster.raster_visibility(twin_mesh, vp, raster.CULL_FRONT, empty_vis, twin_ws)   # cleared, nothing drawn
 
@@ -132,10 +136,18 @@ def main():
             "resolve_vertex_plus_clear_us": lambda tw=tw, o=o: raster.gbuffer_resolve_draws(g, tw, sc["materials"], M,
                                                                                             empty_vis, *gb(o))}
 
-    # ---- the three forms give the same images
+    pm, pm_twin, mo = forms["per_material"], twins["per_material"], out["per_material_motion"]
+    calls["per_material_motion"] = {
+        "resolve_us": lambda: raster.gbuffer_resolve_draws_motion(g, pm, previous, sc["materials"], M,
+                                                                  out["per_material"]["vis"], *gb(mo)),
+        "resolve_vertex_plus_clear_us": lambda: raster.gbuffer_resolve_draws_motion(g, pm_twin, previous, sc["materials"], M,
+                                                                                    empty_vis, *gb(mo))}
+
+    # ---- the forms give the same images
     for name in calls:
         for k in ("visibility_us", "shadow_us", "resolve_us"):
-            calls[name][k]()
+            if k in calls[name]:
+                calls[name][k]()
     torch.cuda.synchronize()
     ref = out["mesh"]
     covered = (ref["vis"] & 0xFFFFFFFF) != 0xFFFFFFFF
@@ -143,6 +155,8 @@ def main():
            "covered": round(float(covered.float().mean()), 4), "build_us": build_us}
     for k in ("vis", "shadow", "depth", "albedo", "emissive", "normal", "velocity"):
         assert torch.equal(out["per_material"][k], ref[k]), ("per_material", k)
+    for k in ("depth", "albedo", "emissive", "normal", "velocity"):
+        assert torch.equal(mo[k], ref[k]), ("per_material_motion", k)
     for k in ("vis", "shadow", "depth", "velocity"):        # what does not depend on the material
         assert torch.equal(out["one_draw"][k], ref[k]), ("one_draw", k)
     mat0 = covered & (torch.from_numpy(mats.astype(np.int64)).to(dev)[(0xFFFFFFFE - (ref["vis"] & 0xFFFFFFFF)).clamp(0, T - 1)] == 0)
@@ -168,13 +182,17 @@ def main():
         return us
     res["us"] = {}
     for k in ("vertex_setup_us", "visibility_us", "shadow_us", "resolve_us", "resolve_vertex_plus_clear_us"):
-        for name in ("mesh", "one_draw", "per_material", "mesh"):          # the baseline twice: its own spread
+        for name in ("mesh", "one_draw", "per_material", "per_material_motion", "mesh"):   # the baseline twice: its own spread
+            if k not in calls[name]:
+                continue
             key = name if name not in res["us"] or k not in res["us"][name] else name + "_again"
             res["us"].setdefault(key, {})[k] = timed(calls[name][k])
         print(k, {n: res["us"][n][k] for n in res["us"] if k in res["us"][n]}, flush=True)
     med = lambda v: float(np.median(v))   # noqa: E731
     res["ratio_to_mesh"] = {n: {k: round(med(res["us"][n][k]) / med(res["us"]["mesh"][k]), 3) for k in res["us"][n]}
-                            for n in ("one_draw", "per_material", "mesh_again")}
+                            for n in ("one_draw", "per_material", "per_material_motion", "mesh_again")}
+    res["motion_to_per_material"] = {k: round(med(v) / med(res["us"]["per_material"][k]), 3)
+                                     for k, v in res["us"]["per_material_motion"].items()}
     print(json.dumps(res), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
