@@ -469,8 +469,17 @@ typedef struct soc_renderer soc_renderer;
  * is the critical path (a high-priority sky lane: soc_renderer_side_queue() == 1, and the lane probe's high-priority
  * windows); the chain's fourth pass then records nothing and the
  * full-resolution bloom output (images.bloom_output, or the emissive image in place) is NOT written. Composition
- * declares BLOOM_MIP1 besides the bloom output. Applies with the weighted chain and the fused histogram's pair path. A
- * caller that reads the bloom output leaves the flag off. */
+ * declares BLOOM_MIP1 and BLOOM_MIP3 besides the bloom output. Applies with the weighted chain and the fused histogram's
+ * pair path. A caller that reads the bloom output leaves the flag off.
+ * In the other frames of such a renderer (a low-priority sky lane) the fourth pass runs, but SPARSE: the chain's output
+ * is a function of BLOOM_MIP3 alone, and where the mip3 texels that reach an aligned 32 x 16 output cell all have the
+ * bit pattern 0x0000 in their RGB halves, the cell is (+0, +0, +0, 1) whichever kernel computes it. The fourth pass
+ * stores nothing in a 62 x 16 strip whose cells are all such, and Composition tests the same cells on the same mip3 and
+ * takes the constant there instead of loading the bloom output, so the colour bits are the same and the bloom output
+ * keeps stale or unwritten pixels in those cells. Only when Composition is the one pass of the graph that declares
+ * BLOOM_OUTPUT (a caller's pass that reads or writes it gets every pixel written), images.bloom_output is set, and the
+ * frame's Composition takes the pair path; SOC_BLOOM_SPARSE=0 (tuning knob) writes and loads every pixel.
+ * soc_bloom_weighted_stage itself always writes its whole output. */
 #define SOC_RENDERER_BLOOM_IN_COMPOSITION 1024
 /* The sky lane's hardware queue (soc_renderer_side_queue): a low-priority stream by default (frames whose main lane is
  * the critical path, e.g. the Sponza frames at 4K); SOC_RENDERER_SKY_LANE_HIGH a high-priority stream (sky-bound frames:

@@ -200,6 +200,14 @@ def bloom_weighted_stage(g, emissive, mips, output, stage=0, stream=None):
                                           _stream(stream)), "bloom_weighted_stage")
 
 
+def bloom_zero_cell_footprint(a: int, b: int, w3: int, h3: int):
+    """(x0, x1, y0, y1), inclusive: the texels of a w3 x h3 mip3 that the 32 x 16 output cell (a, b) of the weighted
+    bloom chain depends on (the host side of the kernels' zero-cell proof, SOC_BLOOM_SPARSE). Needs no GPU."""
+    out = (C.c_int32 * 4)()
+    lib().soc_debug_bloom_zero_cell_footprint(int(a), int(b), int(w3), int(h3), out)
+    return tuple(out)
+
+
 def read_image(t, stream=None) -> np.ndarray:
     """Device image (torch tensor view) -> host numpy array of the same shape (soc_read_image), synchronised."""
     host = np.empty(tuple(t.shape), dtype=t.cpu().numpy().dtype if t.numel() == 0 else

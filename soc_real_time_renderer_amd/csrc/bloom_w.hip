@@ -33,7 +33,23 @@ bool bloom_fused_applicable(const soc_img& emissive, const soc_img* mips, int mi
             return false;
     return true;
 }
+
+// The last stage may leave proven-zero strips unwritten (launch_bloom_weighted's sparse_output): the register-form W4
+// with the zero skip, unless SOC_BLOOM_SPARSE=0 (the dense launches, for A/B).
+bool bloom_sparse_applicable() {
+    return tuning_knob("SOC_BLOOM_SPARSE", 1) != 0 && tuning_knob("SOC_BLOOM_ZERO_SKIP", 1) != 0 &&
+           tuning_knob("SOC_BLOOM_UP10_REG", 1) != 0;
+}
 }  // namespace soc
+
+// Test hook (no GPU needed): the mip3 footprint {x0, x1, y0, y1} (inclusive) of cell (a, b) for a w3 x h3 mip3.
+extern "C" void soc_debug_bloom_zero_cell_footprint(int32_t a, int32_t b, int32_t w3, int32_t h3, int32_t out[4]) {
+    const soc::CellFootprint f = soc::zero_cell_footprint(a, a, b, w3, h3);
+    out[0] = f.x0;
+    out[1] = f.x1;
+    out[2] = f.y0;
+    out[3] = f.y1;
+}
 
 namespace soc {
 namespace {
@@ -662,13 +678,22 @@ __device__ __forceinline__ uint32_t up_from_right(uint32_t v) {  // lane i <- la
 // is +0 in every lane (sums of fma(+0, w > 0, +0), the DPP neighbours included), so the strip's leading output rows
 // skip the 1:2 sums, the shifts and the combine and store pack3(+0, +0, +0): the same bits. The mip1 loads stay: they
 // are the evidence.
-template <bool ZS>
-__global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int nwx, int nwaves) {
+// SP (SOC_BLOOM_SPARSE, the render graph's launch only; needs ZS): a strip whose cells (bloom_w.hpp: at most 3, the
+// strip's 62 columns x one cell row) are all proven zero from mip3 returns before its first mip1 load and stores nothing;
+// Composition, the output's only reader then, takes the constant in the same cells. Any other strip runs as without SP
+// and stores every pixel of it.
+template <bool ZS, bool SP = false>
+__global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int nwx, int nwaves, DImg S3) {
+    static_assert(!SP || (ZS && R_TH == kCellH && R_OW <= 2 * kCellW), "a strip is one cell row and at most 3 cells wide");
     const int lane = (int)(threadIdx.x & 63);
     const int wid = (int)blockIdx.x * (kWorkgroup / 64) + (int)(threadIdx.x >> 6);
     if (wid >= nwaves) return;   // wave-uniform
     const int W0 = O.w, H0 = O.h, W1 = S1.w, H1 = S1.h;
     const int wx = wid % nwx, Y0 = (wid / nwx) * R_TH;
+    if constexpr (SP) {
+        const int xl = min(wx * R_OW + R_OW - 1, W0 - 1);   // the strip's last output column
+        if (zero_cells<3>(S3, wx * R_OW / kCellW, xl / kCellW, Y0 / kCellH, lane)) return;   // wave-uniform
+    }
     const int x = wx * R_OW - 1 + lane;
     const int cx = clampi(x, 0, W0 - 1);
     const int px = cx & 1, c0 = (cx >> 1) - 2 + px;
@@ -793,7 +818,8 @@ bool a16(const soc_img& im) { return im.pitch_bytes % 16 == 0 && reinterpret_cas
 
 }  // namespace
 
-int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage) {
+int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage,
+                          bool sparse_output) {
     const DImg E = dimg(emissive), M1 = dimg(mips[1]), M3 = dimg(mips[3]), O = dimg(output);
     const int swz = 1;   // XCD-aware order: halo re-reads served by L2 (2.0x -> 1.0x HBM traffic)
     // all-zero tiles / rows skip their filters (bloomw_down01p, bloomw_up10r): 0 = every tile filtered, the same bits
@@ -835,12 +861,16 @@ int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const so
     }
     if (stage == 0 || stage == 4) {
         dim3 g(ceil_div(output.width, U_OW), ceil_div(output.height, U_OH));
+        if (sparse_output && !bloom_sparse_applicable())
+            return set_error(SOC_E_INVALID_ARG, "bloom_weighted: the sparse output needs the register-form last stage and the zero skip");
         if (tuning_knob("SOC_BLOOM_UP10_REG", 1)) {
             const int nwx = ceil_div(output.width, R_OW), nwaves = nwx * ceil_div(output.height, R_TH);
-            if (zero_skip)
-                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<true>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves);
+            if (sparse_output)   // proven-zero strips store nothing (bloom_sparse_applicable held: zero_skip and this form)
+                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<true, true>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves, M3);
+            else if (zero_skip)
+                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<true>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves, M3);
             else
-                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<false>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves);
+                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<false>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves, M3);
         } else if (tuning_knob("SOC_BLOOM_UP_SEP", 1))
             launch("bloomw_up10s", kWorkgroup, bloomw_up10s, g, kWorkgroup, 0, s, M1, O, a16(output), swz, zero_skip);
         else

@@ -50,6 +50,67 @@ __device__ __forceinline__ uint32_t load_tile(const DImg& im, int ox, int oy, ui
     return nz;
 }
 
+// ---- zero cells (SOC_BLOOM_SPARSE) ------------------------------------------------------------------------------------
+// The chain's output is a function of mip3 alone (W3: mip3 -> [mip2] -> mip1, W4: mip1 -> [mip0] -> output, the upsweep
+// overwriting its targets). A cell is Composition's workgroup tile: kCellW x kCellH output pixels, aligned. Cell (a, b)'s
+// outputs depend on the mip3 texels of columns clamp(4a - 3 .. 4a + 6) and rows clamp(2b - 3 .. 2b + 4) only (the 1:1
+// up reads x - 1 .. x + 1, the 1:2 up k - 2 .. k + 1 for an even output and k - 1 .. k + 2 for an odd one; clamping only
+// narrows a range; tests/test_bloom_zero_cell.py). If every RGB half of that footprint is 0x0000 the cell is PROVEN:
+// every output pixel of it is pack3(+0, +0, +0) (sums of fma(+0, w > 0, +0)), whichever kernel computes it.
+// The last upsample (sparse bloomw_up10r) and Composition both decide per whole cell with these functions on the same
+// mip3 (nothing writes it between W2 and Composition, and both run in stream order): a strip stores nothing only if every
+// cell it overlaps is proven, and Composition takes the constant in place of its load only in a proven cell, so a pixel
+// Composition loads was stored. A finer or differently aligned region in either kernel would break that.
+constexpr int kCellW = 32, kCellH = 16;
+struct CellFootprint {
+    int x0, x1, y0, y1;   // inclusive mip3 texel ranges
+};
+__host__ __device__ constexpr int cell_clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+// the mip3 (w3 x h3) footprint of the cells (a0..a1, b)
+__host__ __device__ constexpr CellFootprint zero_cell_footprint(int a0, int a1, int b, int w3, int h3) {
+    return CellFootprint{cell_clamp(4 * a0 - 3, 0, w3 - 1), cell_clamp(4 * a1 + 6, 0, w3 - 1),
+                         cell_clamp(2 * b - 3, 0, h3 - 1), cell_clamp(2 * b + 4, 0, h3 - 1)};
+}
+// Whether the cells (a0..a1, b), a1 - a0 < NC, are all proven: the wave's lanes load the union footprint (at most
+// 4 NC + 6 columns x 8 rows; an index past the union repeats a clamped texel of it), OR the RGB halves, one ballot.
+// Wave-uniform; called by all 64 lanes. mip3 is 1/64 of the output: these loads hit the cache. In two halves, so that a
+// caller can issue its other loads between them: the taps are unconditional loads issued back to back, and only the vote
+// waits for them (a predicated tap per round put one memory latency per round in front of everything after it).
+template <int NC>
+struct ZeroCellTaps {
+    static constexpr int TW = 4 * NC + 6, TH = 8, N = (TW * TH + 63) / 64;
+    uint2 t[N];
+};
+template <int NC>
+__device__ __forceinline__ void zero_cells_load(const DImg& m3, int a0, int a1, int b, int lane, ZeroCellTaps<NC>& z) {
+    constexpr int TW = ZeroCellTaps<NC>::TW, TH = ZeroCellTaps<NC>::TH;
+    const CellFootprint f = zero_cell_footprint(a0, a1, b, m3.w, m3.h);
+#pragma unroll
+    for (int k = 0; k < ZeroCellTaps<NC>::N; ++k) {
+        const int i = min(64 * k + lane, TW * TH - 1), r = i / TW, c = i - r * TW;
+        z.t[k] = row_ptr<uint2>(m3, min(f.y0 + r, f.y1))[min(f.x0 + c, f.x1)];
+    }
+}
+template <int NC, bool PIN = true>
+__device__ __forceinline__ bool zero_cells_vote(const ZeroCellTaps<NC>& z) {
+    uint32_t nz = 0u;
+#pragma unroll
+    for (int k = 0; k < ZeroCellTaps<NC>::N; ++k) {
+        uint2 t = z.t[k];
+        // PIN: the taps are first used here, behind the caller's loads (without it the alpha mask of the first tap, and
+        // the wait for it, moved up to the taps' own loads)
+        if constexpr (PIN) asm volatile("" : "+v"(t.x), "+v"(t.y)::"memory");
+        nz |= t.x | (t.y & 0xffffu);   // alpha plays no part
+    }
+    return __ballot(nz != 0u) == 0ull;
+}
+template <int NC>
+__device__ __forceinline__ bool zero_cells(const DImg& m3, int a0, int a1, int b, int lane) {
+    ZeroCellTaps<NC> z;
+    zero_cells_load<NC>(m3, a0, a1, b, lane, z);
+    return zero_cells_vote<NC, false>(z);
+}
+
 // up 1:2 weights: k = 0..3 along the 4-texel footprint
 __device__ __forceinline__ constexpr float u12_w(int parity, int k) {
     constexpr int E[4] = {1, 5, 7, 3}, O[4] = {3, 7, 5, 1};

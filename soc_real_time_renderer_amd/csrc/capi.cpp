@@ -713,6 +713,11 @@ struct soc_renderer {
     bool sky_split = false, sky_split_active = false;
     bool bloom_in_comp = false;          // SOC_RENDERER_BLOOM_IN_COMPOSITION applies to this graph
     bool bloom_in_comp_ok = false;       // ... and the fused pair path applies at this frame's globals resolution
+    // SOC_BLOOM_SPARSE. bloom_sparse: the graph allows it (bloom_in_comp, and Composition is the only pass besides the
+    // chain's last stage that declares the bloom-output resource). Per frame, set before the passes are issued so that
+    // both callbacks see one decision: bloom_sparse_frame, the last stage leaves proven-zero strips unwritten;
+    // bloom_cells_frame, Composition is handed mip3 and proves its cells (that frame, or beside the in-kernel bloom).
+    bool bloom_sparse = false, bloom_sparse_frame = false, bloom_cells_frame = false;
     // the caller's stream is ordered after all second-lane work of the previous call (its join or an equivalent wait)
     bool main_after_side = true;
     // SOC_RENDERER_STATIC_INPUTS: a call of this graph has completed, so the frame inputs the caller wrote before its
@@ -889,6 +894,9 @@ void build_passes(soc_renderer* r) {
             add_pass(r, names[st - 1], "Bloom", pre, rd[st - 1], wr[st - 1], [r, st](const soc_globals* g, hipStream_t s) {
                 if (st == 4 && bloom_in_comp_active(r)) return (int)SOC_OK;   // Composition computes it this frame
                 const soc_img& dst = r->img.bloom_output.data ? r->img.bloom_output : r->img.emissive;
+                // SOC_BLOOM_SPARSE: strips proven zero from mip3 are left unwritten; Composition proves the same cells
+                if (st == 4 && r->bloom_sparse_frame)
+                    return soc::launch_bloom_weighted(r->img.emissive, r->img.bloom_mips, dst, s, 4, true);
                 return soc_bloom_weighted_stage(g, r->img.emissive, r->img.bloom_mips, 4, dst, st, (soc_stream)s);
             });
         return;
@@ -963,7 +971,7 @@ void build_passes_tail(soc_renderer* r) {
     // renderer.cpp:1103-1117 (composition uses) and 1155-1162 (histogram): one launch by default (the colour
     // is binned as it is written), two with SOC_RENDERER_UNFUSED_HISTOGRAM (measured in composition.hip)
     const uint64_t comp_reads = res_mask({SOC_RES_ALBEDO, em_res, SOC_RES_NORMAL, SOC_RES_DEPTH, SOC_RES_SSAO_BLUR,
-                                          SOC_RES_SUN_SHADOW}) | (r->bloom_in_comp ? res_mask({SOC_RES_BLOOM_MIP1}) : 0) |
+                                          SOC_RES_SUN_SHADOW}) | (r->bloom_in_comp ? res_mask({SOC_RES_BLOOM_MIP1, SOC_RES_BLOOM_MIP3}) : 0) |
                                 (r->sky_split ? 0 : res_mask({SOC_RES_CLOUDS}));
     if (fused_hist) {
         add_pass(r, "Composition+GenerateLuminanceHistogram", "Composition", pre, comp_reads,
@@ -974,7 +982,8 @@ void build_passes_tail(soc_renderer* r) {
                                                                  I.ssao_blur, I.shadow, I.clouds, I.auto_exposure,
                                                                  r->hist_scratch, false, (soc_stream)s,
                                                                  r->sky_split_active,
-                                                                 bloom_in_comp_active(r) ? &I.bloom_mips[1] : nullptr);
+                                                                 bloom_in_comp_active(r) ? &I.bloom_mips[1] : nullptr,
+                                                                 r->bloom_cells_frame ? &I.bloom_mips[3] : nullptr);
                  });
         // the 8 partial histograms of the fused launch into the AutoExposure bins. Before a multi-GPU exchange
         // (PRE and POST in separate calls) the fold must precede it; in a one-call frame the resolve folds them
@@ -1207,6 +1216,14 @@ int build_graph(soc_renderer* r) {
     build_passes(r);
     build_passes_tail(r);
     int rc = insert_user_passes(r);
+    // SOC_BLOOM_SPARSE needs a graph in which nobody but Composition reads the bloom output (a caller's pass that
+    // declares it, or the in-place output that is the emissive image, gets every pixel written)
+    r->bloom_sparse = r->bloom_in_comp && r->img.bloom_output.data;
+    for (const auto& p : r->passes) {
+        const uint64_t bo = 1ull << SOC_RES_BLOOM_OUTPUT;
+        if ((p.reads & bo) && p.name != "Composition+GenerateLuminanceHistogram") r->bloom_sparse = false;
+        if ((p.writes & bo) && p.name != "BloomUpsample - 1+0") r->bloom_sparse = false;
+    }
     derive_dependencies(r);
     derive_signals(r);
     return rc;
@@ -1538,15 +1555,27 @@ extern "C" int soc_renderer_execute(soc_renderer* r, const soc_globals* g, int32
         if (hipEventRecord(r->fork_ev, s) != hipSuccess)
             return set_error(SOC_E_HIP, "soc_renderer_execute: second lane fork failed");
     }
+    if (phase & SOC_PHASE_PRE_EXPOSURE) {
+        // SOC_BLOOM_SPARSE, decided once per frame (after the lane probe, like bloom_in_comp_active): the pair path at this
+        // frame's resolution (a generic-path Composition reads every pixel of the bloom output) and the knobs; the sparse
+        // last stage only where the in-kernel bloom does not replace it
+        const bool cells = r->bloom_in_comp && r->bloom_in_comp_ok && soc::bloom_sparse_applicable();
+        r->bloom_sparse_frame = cells && r->bloom_sparse && !bloom_in_comp_active(r);
+        r->bloom_cells_frame = cells && (r->bloom_sparse_frame || bloom_in_comp_active(r));
+    }
     // issue order (tuning knob SOC_RENDERER_SSAO_FIRST): the AO passes move within the main lane, ahead of passes they do
     // not depend on (same passes, same per-pass results). Default (-1): just before the last bloom pass, so SSAO's
     // 1024-lane workgroups start once the small bloom mips are done and overlap the sky lane's density / sun-visibility
     // kernels with the full-resolution upsample after them (C3 1370-1380 -> 1446-1451 fps, C2 +6 %, C4 +1 % against
     // AO first). 1: AO first; 0: registration order (AO after every bloom pass); k >= 2: after
-    // k - 1 other passes.
+    // k - 1 other passes. In a frame whose last bloom stage is sparse (SOC_BLOOM_SPARSE) the default is the registration
+    // order: of the full-resolution upsample that -1 places behind the AO passes only the unproven strips are left, and with
+    // the benchmark's all-zero emissive the chain in one piece measured C3 1965-1976 fps against 1937-1943 with -1 (the
+    // parent's dense last stage: 1940-1945 with -1, 1897-1911 with 0); the box atrium's lamps 2450-2460 either way
+    // (profiles/r09_ab_bloom_sparse.txt).
     std::vector<int> order(n);
     for (int i = 0; i < n; ++i) order[i] = i;
-    const int ao_pos = tuning_knob("SOC_RENDERER_SSAO_FIRST", -1);
+    const int ao_pos = tuning_knob("SOC_RENDERER_SSAO_FIRST", r->bloom_sparse_frame ? 0 : -1);
     if (ao_pos) {
         std::vector<int> ao, rest;
         for (int i = 0; i < n; ++i) (r->passes[i].group == "Ambient Occlusion" ? ao : rest).push_back(i);

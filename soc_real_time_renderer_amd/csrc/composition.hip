@@ -37,6 +37,7 @@ struct CompParams {
     int sky_external;      // 1: sky pixels (depth == 1) are written and binned by sky_compose_pair (second lane)
     float rw, rh;          // recip_rn(target extent) for the pixel-centre uv (div_rn)
     int bloom_zero_skip;   // SOC_BLOOM_ZERO_SKIP: the in-kernel bloom skips its sums on all-zero mip1 tiles (BL)
+    int bloom_sparse;      // SOC_BLOOM_SPARSE: the workgroup's cell is tested against mip3 (zero_cells, bloom_w.hpp)
 };
 
 __device__ __forceinline__ float fast_pow(float x, float y) {
@@ -256,12 +257,17 @@ constexpr int BX = 64, BY = 4;
 // is computed for the workgroup's 32 x 16 tile in LDS (Up10Tile, bloom_w.hpp: the same values per pixel, rounded to
 // RGBA16F as the chain stores its output) while the G-buffer loads are in flight, and used as the emissive input, so
 // the full-resolution bloom output is neither written by the chain nor read back here (16 B/px). `emissive` unused.
+// p.bloom_sparse (SOC_BLOOM_SPARSE, the render graph only): the workgroup's 32 x 16 tile is a cell of bloom_w.hpp; each
+// wave tests the cell's mip3 footprint itself (no LDS, no barrier; the four waves load the same texels and agree). In a
+// proven cell the bloom is pack3(+0, +0, +0) without the `emissive` load (the sparse last stage left those pixels
+// unwritten) or, with BL, without the mip1 tile and its barriers; any other cell runs as without the flag.
 #ifndef SOC_COMP_LIGHT_WAVES
 #define SOC_COMP_LIGHT_WAVES 6
 #endif
-template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false>
+template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false>
 __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGHTS && !BL ? SOC_COMP_LIGHT_WAVES : 1))) void composition_pair(DImg target, DImg albedo, DImg emissive, DImg normal, DImg depth,
-                                                        DImg ssao, DImg shadow, DImg clouds, CompParams p, DImg mip1) {
+                                                        DImg ssao, DImg shadow, DImg clouds, CompParams p, DImg mip1, DImg mip3) {
+    static_assert(!SP || ((LIGHTS || BL) && HIST), "SP: the LIGHTS / BL kernels' form of p.bloom_sparse (the render graph's launches)");
     static_assert(!BL || HIST, "the in-kernel bloom runs in the fused-histogram kernel (no early exit before its barriers)");
     // a wave covers 16x8 pixels (8 lanes x 2 pixels per row, 8 rows): every row segment is one
     // 128-B line of each G-buffer image, and the wave's shadow-map taps form a compact 2D patch
@@ -276,6 +282,16 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
     const int x = bx * 32 + (wave & 1) * 16 + (lane & 7) * 2;
     const int y = by * 16 + (wave >> 1) * 8 + (lane >> 3);
     const bool inside = x < target.w && y < target.h;
+    static_assert(kCellW == 32 && kCellH == 16, "the workgroup's tile is the bloom's cell");
+    // the cell's mip3 taps, issued ahead of the G-buffer loads; the vote that waits for them follows those loads
+    // (the lights and in-kernel-bloom kernels take the flag as the template parameter SP: the runtime branch cost them
+    // registers, and occupancy with them; HIST: the render graph's launches, where no lane leaves before the vote)
+    const bool prove = HIST && ((LIGHTS || BL) ? SP : p.bloom_sparse != 0);   // wave-uniform
+    ZeroCellTaps<1> zt = {};
+    if (prove) zero_cells_load<1>(mip3, bx, bx, by, lane, zt);
+    // the lights kernels vote at once: the taps held across the G-buffer loads cost them registers they do not have
+    bool bloom_zero = false;
+    if (LIGHTS && prove) bloom_zero = zero_cells_vote<1, false>(zt);
     if (!HIST && !inside) return;
     uint2 outp[2] = {uint2{0u, 0u}, uint2{0u, 0u}};
     uint32_t own = 3u;   // bit k: this kernel writes (and bins) pixel k of the pair
@@ -286,25 +302,29 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
     // once-read streams non-temporal (NT & 1: keep L2 for the shadow-map / AO gathers); aux bit 1 = nt
     constexpr int ld_aux = (NT & 1) ? 2 : 0;
     float2 d2 = float2{0.0f, 0.0f};
-    uint4 a4 = uint4{0u, 0u, 0u, 0u}, e4 = a4, n4 = a4;
+    uint4 a4 = uint4{0u, 0u, 0u, 0u}, n4 = a4;
+    const uint2 bz = pack3(C3{0.0f, 0.0f, 0.0f});
+    uint4 e4 = uint4{bz.x, bz.y, bz.x, bz.y};   // the bloom of a proven cell, unless loaded (or computed, BL) below
     // NT & 4: both pixels' AO taps (3 half-res texels per row) as one 8-B load per row, issued with the G-buffer
     // loads (not after the depth test), for sky pixels too (in bounds, unused); the same bits as sample_r8
     float aop[2] = {0.0f, 0.0f};
     if (inside) {
         d2 = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(bd.r, buf_row(bd, y) + x * 4, 0, ld_aux));
         a4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ba.r, buf_row(ba, y) + x * 8, 0, ld_aux));
-        if (!BL) e4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(be.r, buf_row(be, y) + x * 8, 0, ld_aux));
+        if (!BL && (LIGHTS ? !bloom_zero : !prove)) e4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(be.r, buf_row(be, y) + x * 8, 0, ld_aux));
         n4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(bn.r, buf_row(bn, y) + x * 8, 0, ld_aux));
         if (NT & 4) sample_r8_pair(bo, centre_uv_rn(x, target.w, p.rw), centre_uv_rn(x + 1, target.w, p.rw), v, aop[0], aop[1]);
     }
+    // wave-uniform, by all 64 lanes; the emissive load it decides comes one latency after the others in an unproven cell
+    if (!LIGHTS && prove) bloom_zero = zero_cells_vote<1>(zt);
+    if (!BL && !LIGHTS && prove && !bloom_zero && inside)
+        e4 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(be.r, buf_row(be, y) + x * 8, 0, ld_aux));
     if constexpr (BL) {   // every lane takes part in the tile's barriers; the pair's bloom as the chain stores it
         __shared__ Up10Tile<32, 16> bl;
         const int X0 = bx * 32, Y0 = by * 16;
-        // an all-zero mip1 tile (SOC_BLOOM_ZERO_SKIP): the pair is pack3(+0, +0, +0) without the tile's sums
-        if (bl.build(mip1, X0, Y0, target.w, target.h, threadIdx.x, p.bloom_zero_skip != 0)) {
-            const uint2 b0 = pack3(C3{0.0f, 0.0f, 0.0f});
-            e4 = uint4{b0.x, b0.y, b0.x, b0.y};
-        } else {
+        // a proven cell (workgroup-uniform: every wave computed the same proof, so none reaches build's barriers), or an
+        // all-zero mip1 tile (SOC_BLOOM_ZERO_SKIP): the pair is pack3(+0, +0, +0) without the tile's sums
+        if (!bloom_zero && !bl.build(mip1, X0, Y0, target.w, target.h, threadIdx.x, p.bloom_zero_skip != 0)) {
             C3 o[2];
             bl.out(y - Y0, x - X0, o);
             const uint2 b0 = pack3(o[0]), b1 = pack3(o[1]);
@@ -479,10 +499,12 @@ namespace {
 // (returns 1 otherwise, having launched nothing)
 // bloom_mip1 != nullptr (the render graph under SOC_RENDERER_BLOOM_IN_COMPOSITION): the bloom output is computed in the
 // kernel from the chain's mip1 (composition_pair<..., BL>); needs the fused histogram and the pair path.
+// bloom_mip3 != nullptr (the render graph under SOC_BLOOM_SPARSE): cells proven zero from the chain's mip3 take the
+// constant in place of the `emissive` load (the sparse last stage did not write them) or of the in-kernel upsample.
 int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo, soc_img emissive,
                        soc_img normal, soc_img depth, soc_img ssao, soc_img shadow, soc_img clouds, uint32_t* bins,
                        uint32_t* scratch, soc_stream stream, bool fold = true, bool sky_external = false,
-                       const soc_img* bloom_mip1 = nullptr) {
+                       const soc_img* bloom_mip1 = nullptr, const soc_img* bloom_mip3 = nullptr) {
     static const char* P = "soc_composition";
     if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
     int rc = check_img(target, SOC_FMT_RGBA16F, P, "target");
@@ -542,42 +564,62 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
         if (!bins || !fast || bloom_mip1->width * 2 != W || bloom_mip1->height * 2 != H)
             return set_error(SOC_E_SHAPE, "%s: the in-kernel bloom needs the fused histogram's pair path and mip1 = W/2 x H/2", P);
     }
+    if (bloom_mip3) {
+        rc = check_img(*bloom_mip3, SOC_FMT_RGBA16F, P, "bloom mip3");
+        if (rc) return rc;
+        if (!bins || !fast || bloom_mip3->width * 8 != W || bloom_mip3->height * 8 != H)
+            return set_error(SOC_E_SHAPE, "%s: the bloom's zero cells need the fused histogram's pair path and mip3 = W/8 x H/8", P);
+    }
+    p.bloom_sparse = bloom_mip3 != nullptr;
+    const DImg m3 = bloom_mip3 ? dimg(*bloom_mip3) : DImg{};
     if (fast) {
         dim3 grd(ceil_div(W, 32), ceil_div(H, 16));
         const bool lights = (p.npl | p.nsl) != 0;
 #define SOC_COMP_PAIR(HI, LI) launch("composition_pair", kWorkgroup, composition_pair<HI, LI>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), \
-            dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{})
+            dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3)
         if (bins) {
             p.bins = scratch;
             p.sky_external = sky_external ? 1 : 0;
             p.lmin = g->log_min_luminance;
             p.lrange = g->log_max_luminance - g->log_min_luminance;
             p.bf = bin_fast_params(p.lmin, p.lrange);
-            if (bloom_mip1 && lights)
+            if (bloom_mip1 && lights && bloom_mip3)
+                launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, true, true>, grd, kWorkgroup, 0, hs(stream),
+                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
+                       dimg(clouds), p, dimg(*bloom_mip1), m3);
+            else if (bloom_mip1 && lights)
                 launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, true>, grd, kWorkgroup, 0, hs(stream),
                        dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, dimg(*bloom_mip1));
+                       dimg(clouds), p, dimg(*bloom_mip1), m3);
+            else if (bloom_mip1 && bloom_mip3)
+                launch("composition_pair", kWorkgroup, composition_pair<true, false, 7, true, true>, grd, kWorkgroup, 0, hs(stream),
+                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
+                       dimg(clouds), p, dimg(*bloom_mip1), m3);
             else if (bloom_mip1)
                 launch("composition_pair", kWorkgroup, composition_pair<true, false, 7, true>, grd, kWorkgroup, 0, hs(stream),
                        dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, dimg(*bloom_mip1));
+                       dimg(clouds), p, dimg(*bloom_mip1), m3);
+            else if (lights && bloom_mip3)
+                launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, false, true>, grd, kWorkgroup, 0, hs(stream),
+                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
+                       dimg(clouds), p, DImg{}, m3);
             else if (lights) SOC_COMP_PAIR(true, true);
             else if (nt && aop)
                 launch("composition_pair", kWorkgroup, composition_pair<true, false, 7>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                    dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{});
+                    dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
             else if (nt)
                 launch("composition_pair", kWorkgroup, composition_pair<true, false, 3>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                    dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{});
+                    dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
             else SOC_COMP_PAIR(true, false);
             if (fold) launch("histogram_fold", kBins, histogram_fold, 1, kBins, 0, hs(stream), scratch, bins);
         } else if (nt && !lights && aop) {
             launch("composition_pair", kWorkgroup, composition_pair<false, false, 7>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{});
+                dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
         } else if (nt && !lights) {
             // non-temporal G-buffer loads and colour store (measured at 4K: 71.5 -> 68 us; TAA, the next
             // reader of depth, +3 us: the frame is unchanged). SOC_COMP_NT=0: default cache policy.
             launch("composition_pair", kWorkgroup, composition_pair<false, false, 3>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{});
+                dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
         } else {
             if (lights) SOC_COMP_PAIR(false, true);
             else SOC_COMP_PAIR(false, false);
@@ -637,12 +679,14 @@ extern "C" int soc_composition(const soc_globals* g, const soc_globals* d_global
 int soc::composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target,
                                          soc_img albedo, soc_img emissive, soc_img normal, soc_img depth, soc_img ssao,
                                          soc_img shadow, soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch,
-                                         bool fold, soc_stream stream, bool sky_external, const soc_img* bloom_mip1) {
+                                         bool fold, soc_stream stream, bool sky_external, const soc_img* bloom_mip1,
+                                         const soc_img* bloom_mip3) {
     if (!g || !ae || !scratch)
         return set_error(SOC_E_INVALID_ARG, "soc_composition_luminance_histogram: null globals / auto exposure / scratch");
     int rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds,
-                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1);
+                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1, bloom_mip3);
     if (rc <= 0) return rc;   // launched (or failed validation)
+    if (bloom_mip3) return set_error(SOC_E_SHAPE, "composition: the bloom's zero cells need the pair path");
     if (bloom_mip1) return set_error(SOC_E_SHAPE, "composition: the in-kernel bloom needs the pair path");
     if (sky_external) return set_error(SOC_E_INVALID_ARG, "composition: sky_external needs the pair path");
     // not fusable: the two passes back to back (same results)

@@ -83,14 +83,19 @@ void mat4_mul_host(float out[16], const float a[16], const float b[16]);
 // The bloom chain's exactly-halving mips (bloom_w.hip).
 bool bloom_fused_applicable(const soc_img& emissive, const soc_img* mips, int mip_count, const soc_img& output);
 // Weighted-form bloom chain (bloom_w.hip): same applicability as the fused chain.
-int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage);
+// sparse_output (the render graph's last stage under SOC_BLOOM_SPARSE, when bloom_sparse_applicable()): output strips
+// proven zero from mips[3] are not written; the reader must take the constant there (composition's bloom_mip3).
+int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage,
+                          bool sparse_output = false);
+bool bloom_sparse_applicable();
 
 // soc_composition_luminance_histogram with the fold of the 8 partial histograms optionally left to a
 // separate histogram_fold_launch (the render graph times the fold as a pass of its own).
 int composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
                                     soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
                                     soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch, bool fold, soc_stream stream,
-                                    bool sky_external = false, const soc_img* bloom_mip1 = nullptr);
+                                    bool sky_external = false, const soc_img* bloom_mip1 = nullptr,
+                                    const soc_img* bloom_mip3 = nullptr);
 // The fused pair path applies to these images at the globals' resolution (composition.hip).
 bool composition_pair_applicable(const soc_globals* g, const soc_img& target, const soc_img& albedo,
                                  const soc_img& emissive, const soc_img& normal, const soc_img& depth,
