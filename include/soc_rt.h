@@ -888,6 +888,65 @@ int soc_gbuffer_resolve_draws_motion(const soc_globals* g, const soc_draw_scene*
  * history, so the frame after it has the reference's velocity. */
 int soc_renderer_set_draw_motion(soc_renderer* r, soc_transform* previous_transforms);
 
+/* --- Terrain layer: DrawTerrain / SunShadowDrawTerrain over the raster head (opt-in) ----------
+ * The reference's frame is entities standing on terrain: rebuild_task_graph (renderer.cpp:965-1021) runs DepthPrepass,
+ * SunShadowDraw, SunShadowDrawTerrain, GBufferGeneration and DrawTerrain, and both terrain tasks LOAD the images the
+ * entity tasks wrote and depth-test into them with LESS_OR_EQUAL. The two calls below are those tasks for any soc_mesh
+ * (soc_terrain_tessellate's, or any other).
+ *
+ * soc_draw_terrain. The mesh is rasterised into `visibility` (width*height u64 of `depth`'s extent, cleared by the
+ * call; cull FRONT, the rules and the key of soc_raster_visibility with the globals' camera_projection_view_matrix). A
+ * pixel with a terrain fragment of depth z_t reads the depth image's value z_e; the fragment wins iff z_t <= z_e,
+ * compared on the float bits the key carries (exact; both depths are >= +0, as every depth this library writes), so a
+ * tie goes to the terrain, the later draw. A winning pixel writes depth = z_t and albedo, normal and velocity as
+ * soc_gbuffer_resolve computes them for that triangle and material (the reference's terrain material is
+ * SOC_MATERIAL_ZERO_VELOCITY | SOC_MATERIAL_NORMAL_MAP: velocity (0, 0, 0, 0), draw_terrain.inl:220). There is NO
+ * emissive image: DrawTerrain has three colour attachments (draw_terrain.inl:14-17, 199-201), so where the terrain hides
+ * an entity the emissive image keeps the hidden entity's value, and bloom and composition see it. A losing or empty
+ * pixel writes nothing at all. `workspace` (soc_raster_workspace_size of the mesh) is required: the layer always runs
+ * the vertex stage once per vertex.
+ *
+ * soc_sun_shadow_draw_terrain. Depth-only raster of the mesh into the D32 shadow image, cull BACK and NO depth bias
+ * (sun_shadow_draw_terrain.inl:47-58 has no depth_bias_*), with clear = 0 on top of what is there (the image
+ * SunShadowDraw left): the 32-bit atomicMin gives the per-texel minimum of the two whatever the order. clear = 1 clears
+ * to 1.0 first, for a frame whose head draws no shadow; it then equals soc_raster_depth with bias 0 / 0.
+ * Quirk Q15: the reference's shadow terrain ignores terrain_offset (its vertex is (u sx, 0 + height, v sz),
+ * sun_shadow_draw_terrain.inl:112, against draw_terrain.inl:141), so with a non-zero offset its shadow is not under
+ * its terrain. Both calls take a mesh, so a caller who wants the quirk tessellates a second mesh with a globals copy
+ * whose terrain_offset is zero (x - 0.0f is exact) and passes that one here; the default offset is zero and one mesh
+ * serves both.
+ *
+ * Every refusal is made on the host before the first HIP call, with soc_last_error_string() set: a null mesh,
+ * visibility or workspace and check failures of the mesh (SOC_E_INVALID_ARG; SOC_E_SHAPE for too many triangles),
+ * material_count <= 0, images of wrong formats (SOC_E_INVALID_ARG) or differing extents (SOC_E_SHAPE). */
+int soc_draw_terrain(const soc_globals* g, const soc_mesh* mesh, const soc_material* d_materials,
+                     int32_t material_count, uint64_t* visibility /* W*H, cleared by the call */,
+                     soc_img depth, soc_img albedo, soc_img normal, soc_img velocity,
+                     void* workspace, soc_stream stream);
+int soc_sun_shadow_draw_terrain(const soc_mesh* mesh, const float view_projection[16], int32_t clear,
+                                soc_img depth, void* workspace, soc_stream stream);
+typedef struct soc_terrain_layer {
+    soc_mesh mesh;                  /* camera view; device arrays (soc_terrain_tessellate, or any mesh) */
+    soc_mesh shadow_mesh;           /* positions == NULL: use `mesh` */
+    const soc_material* materials;  /* device */
+    int32_t material_count, shadow;
+    uint64_t* visibility;           /* may be the head's own buffer */
+    void* workspace;                /* soc_raster_workspace_size(mesh) */
+    void* shadow_workspace;         /* of the shadow mesh; required with shadow = 1 */
+} soc_terrain_layer;
+/* The render graph's terrain layer over a raster head (a mesh or a draw scene; SOC_E_INVALID_ARG without one). Adds
+ * "DrawTerrain" directly after "GBufferGeneration" (group "Rendering G-Buffer", reads and writes VISIBILITY, DEPTH,
+ * ALBEDO, NORMAL, VELOCITY, on the caller's stream; it writes the velocity image GBufferGeneration writes) and, with
+ * `shadow`, "SunShadowDrawTerrain" (group "Shadows", reads and writes SUN_SHADOW) directly after "SunShadowDraw" on
+ * that pass's lane with clear = 0, or, when the head draws no shadow, after "DepthPrepass" on the caller's stream with
+ * clear = 1. Dependencies and ring edges are derived from the declared uses as for every pass. The renderer copies the
+ * struct (the arrays stay caller-owned). The layer survives replacing the head by another head; it is removed with the
+ * head (soc_renderer_set_raster_scene / _set_draw_scene with NULL) and by a NULL layer. Per-object motion is
+ * unaffected. The layer's visibility buffer may be the head's (GBufferGeneration has read it by then); its workspaces
+ * are its own. SOC_E_INVALID_ARG for an incomplete layer, shadow = 1 without a shadow_workspace or without
+ * images.shadow. Passes are rebuilt as by soc_renderer_set_raster_scene. */
+int soc_renderer_set_terrain(soc_renderer* r, const soc_terrain_layer* layer);   /* NULL removes it */
+
 /* --- Headless output and metrics (replaces the swapchain present of tone_mapping.inl:
  * 172-176 and the ImGui "GPU Metric" window of renderer.cpp:769-806) ------------------------------- */
 /* The most recent frame's timed passes as one JSON object: {"frame", "total_gpu_ms", "groups" (the 12

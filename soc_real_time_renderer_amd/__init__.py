@@ -478,7 +478,7 @@ class Renderer:
         arrays; None clears it (the G-buffer images are inputs again)."""
         if mesh is None:
             _check(lib().soc_renderer_set_raster_scene(self.handle, None), "soc_renderer_set_raster_scene")
-            self._scene = self._motion = None
+            self._scene = self._motion = self._terrain = None   # the terrain layer goes with the head
             return
         sc = _abi.RasterScene()
         sc.mesh = mesh.struct
@@ -498,7 +498,7 @@ class Renderer:
         per-object motion off; `motion` (a history tensor, see set_draw_motion) turns it on for the new scene."""
         if scene is None:
             _check(lib().soc_renderer_set_draw_scene(self.handle, None, None, 0, 0, None), "soc_renderer_set_draw_scene")
-            self._scene = self._motion = None
+            self._scene = self._motion = self._terrain = None   # the terrain layer goes with the head
             return
         self._scene = (scene, d_materials, visibility)   # keep the arrays alive
         _check(lib().soc_renderer_set_draw_scene(self.handle, C.byref(scene.struct), _ptr(d_materials), int(material_count),
@@ -514,6 +514,31 @@ class Renderer:
         velocity. None turns motion off. The tensor is the caller's: it is not part of save_state / load_state."""
         _check(lib().soc_renderer_set_draw_motion(self.handle, _ptr(previous_transforms)), "soc_renderer_set_draw_motion")
         self._motion = previous_transforms   # keep the array alive
+
+    def set_terrain(self, mesh, d_materials=None, material_count: int = 0, visibility=None, workspace=None,
+                    shadow: bool = True, shadow_mesh=None, shadow_workspace=None):
+        """The terrain layer over the raster head (soc_renderer_set_terrain): "DrawTerrain" after GBufferGeneration
+        and, with `shadow`, "SunShadowDrawTerrain" after SunShadowDraw (after DepthPrepass, clearing, when the head
+        draws no shadow). `mesh` is a raster.MeshBuffers of device arrays (raster.terrain_tessellate's, or any);
+        `visibility` may be the head's buffer; `workspace` is the mesh's own (mesh.workspace()); `shadow_workspace`
+        is required with shadow. `shadow_mesh` (default: `mesh`) is the mesh the shadow pass draws: the reference's
+        ignores terrain_offset (quirk Q15). None removes the layer; it also goes with the head."""
+        if mesh is None:
+            _check(lib().soc_renderer_set_terrain(self.handle, None), "soc_renderer_set_terrain")
+            self._terrain = None
+            return
+        t = _abi.TerrainLayer()
+        t.mesh = mesh.struct
+        if shadow_mesh is not None:
+            t.shadow_mesh = shadow_mesh.struct
+        t.materials = _ptr(d_materials)
+        t.material_count = int(material_count)
+        t.shadow = int(bool(shadow))
+        t.visibility = _ptr(visibility)
+        t.workspace = _ptr(workspace)
+        t.shadow_workspace = _ptr(shadow_workspace)
+        _check(lib().soc_renderer_set_terrain(self.handle, C.byref(t)), "soc_renderer_set_terrain")
+        self._terrain = (mesh, shadow_mesh, d_materials, visibility, workspace, shadow_workspace)   # keep the arrays alive
 
     def metrics_json(self, frame: int = 0) -> str:
         """The last frame's GPU-metric record (renderer.cpp:769-806) as a JSON string (needs timing and a

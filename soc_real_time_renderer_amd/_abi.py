@@ -160,6 +160,13 @@ class DrawSceneStruct(C.Structure):
                 ("material_count", C.c_int32), ("pad", C.c_int32), ("workspace", C.c_void_p)]
 
 
+class TerrainLayer(C.Structure):
+    """soc_terrain_layer: DrawTerrain / SunShadowDrawTerrain over the raster head (soc_renderer_set_terrain)."""
+    _fields_ = [("mesh", Mesh), ("shadow_mesh", Mesh), ("materials", C.c_void_p), ("material_count", C.c_int32),
+                ("shadow", C.c_int32), ("visibility", C.c_void_p), ("workspace", C.c_void_p),
+                ("shadow_workspace", C.c_void_p)]
+
+
 ENTITY_POINT_LIGHT, ENTITY_SPOT_LIGHT = 1, 2
 
 
@@ -201,7 +208,8 @@ STRUCTS = {"soc_img": SocImg, "soc_globals": Globals, "soc_sun_info": SunInfo, "
            "soc_spot_light": SpotLight, "soc_auto_exposure": AutoExposure, "soc_camera": Camera,
            "soc_frame_images": FrameImages, "soc_mesh": Mesh, "soc_material": Material,
            "soc_raster_scene": RasterScene, "soc_pass_desc": PassDesc, "soc_entity": Entity,
-           "soc_transform": Transform, "soc_draw": Draw, "soc_draw_scene": DrawSceneStruct}
+           "soc_transform": Transform, "soc_draw": Draw, "soc_draw_scene": DrawSceneStruct,
+           "soc_terrain_layer": TerrainLayer}
 
 _I = C.c_int
 _P = C.c_void_p
@@ -306,6 +314,9 @@ FUNCTIONS = {
     "soc_gbuffer_resolve_draws_motion": (_I, [_G, C.POINTER(DrawSceneStruct), _P, _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG,
                                               _IMG, _P]),
     "soc_renderer_set_draw_motion": (_I, [_P, _P]),
+    "soc_draw_terrain": (_I, [_G, C.POINTER(Mesh), _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG, _P, _P]),
+    "soc_sun_shadow_draw_terrain": (_I, [C.POINTER(Mesh), C.POINTER(C.c_float), C.c_int32, _IMG, _P, _P]),
+    "soc_renderer_set_terrain": (_I, [_P, C.POINTER(TerrainLayer)]),
 }
 
 # not in the public header: test hooks

@@ -227,6 +227,9 @@ const FieldInfo kFields[] = {
     F(soc_draw_scene, vertex_count), F(soc_draw_scene, index_count), F(soc_draw_scene, draws), F(soc_draw_scene, draw_count),
     F(soc_draw_scene, transform_count), F(soc_draw_scene, transforms), F(soc_draw_scene, material_count),
     F(soc_draw_scene, pad), F(soc_draw_scene, workspace),
+    F(soc_terrain_layer, mesh), F(soc_terrain_layer, shadow_mesh), F(soc_terrain_layer, materials),
+    F(soc_terrain_layer, material_count), F(soc_terrain_layer, shadow), F(soc_terrain_layer, visibility),
+    F(soc_terrain_layer, workspace), F(soc_terrain_layer, shadow_workspace),
     F(soc_entity, position), F(soc_entity, rotation), F(soc_entity, scale), F(soc_entity, components),
     F(soc_entity, color), F(soc_entity, intensity), F(soc_entity, cut_off), F(soc_entity, outer_cut_off),
     F(soc_pass_desc, name), F(soc_pass_desc, group), F(soc_pass_desc, phase), F(soc_pass_desc, flags),
@@ -254,6 +257,7 @@ extern "C" size_t soc_abi_sizeof(const char* t) {
     if (s == "soc_transform") return sizeof(soc_transform);
     if (s == "soc_draw") return sizeof(soc_draw);
     if (s == "soc_draw_scene") return sizeof(soc_draw_scene);
+    if (s == "soc_terrain_layer") return sizeof(soc_terrain_layer);
     if (s == "soc_pass_desc") return sizeof(soc_pass_desc);
     if (s == "soc_entity") return sizeof(soc_entity);
     return 0;
@@ -677,6 +681,10 @@ struct soc_renderer {
     // motion_valid: the array holds the transforms of the previous GBufferGeneration (false until the first one).
     soc_transform* motion_prev = nullptr;
     bool motion_valid = false;
+    // soc_renderer_set_terrain: DrawTerrain / SunShadowDrawTerrain over the head's images (a copy; shadow_mesh resolved to
+    // the mesh the shadow pass draws). Kept across a change of head, dropped with it.
+    soc_terrain_layer terrain{};
+    bool has_terrain = false;
     std::vector<Pass> passes;
     std::vector<UserPass> user_passes;
     uint32_t flags = 0;
@@ -826,6 +834,18 @@ void build_raster_passes(soc_renderer* r) {
                                              1.75f, r->img.shadow, shadow_lane ? r->shadow_ws : r->scene.workspace,
                                              (soc_stream)s);
                  }, shadow_lane ? SOC_PASS_ASYNC : 0);
+    // SunShadowDrawTerrainTask (renderer.cpp:983-990, sun_shadow_draw_terrain.inl): loads the shadow image SunShadowDraw
+    // wrote and draws the terrain into it unbiased, on that pass's lane behind it (the layer's shadow workspace is its
+    // own). A head without a shadow draw: the terrain's is the frame's only one, on the caller's stream, and clears.
+    if (r->has_terrain && r->terrain.shadow) {
+        const bool head_shadow = r->scene.shadow != 0;
+        add_pass(r, "SunShadowDrawTerrain", "Shadows", pre, res_mask({SOC_RES_SUN_SHADOW}), res_mask({SOC_RES_SUN_SHADOW}),
+                 [r, head_shadow](const soc_globals* g, hipStream_t s) {
+                     return soc_sun_shadow_draw_terrain(&r->terrain.shadow_mesh, g->sun_info.projection_view_matrix,
+                                                        head_shadow ? 0 : 1, r->img.shadow, r->terrain.shadow_workspace,
+                                                        (soc_stream)s);
+                 }, head_shadow && shadow_lane ? SOC_PASS_ASYNC : 0);
+    }
     // GBufferGenerationTask uses (renderer.cpp:993-1005): albedo, emissive, normal, velocity, depth
     add_pass(r, "GBufferGeneration", "Rendering G-Buffer", pre, res_mask({SOC_RES_VISIBILITY}),
              res_mask({SOC_RES_ALBEDO, SOC_RES_EMISSIVE, SOC_RES_NORMAL, SOC_RES_VELOCITY, SOC_RES_DEPTH}),
@@ -861,6 +881,18 @@ void build_raster_passes(soc_renderer* r) {
                                             r->scene.visibility, I.depth, I.albedo, I.emissive, I.normal,
                                             frame_velocity(r), r->scene.workspace, (soc_stream)s);
              });
+    // DrawTerrainTask (renderer.cpp:1007-1021, draw_terrain.inl): loads the images GBufferGeneration wrote and depth-tests
+    // the terrain into them (albedo, normal, velocity, depth; no emissive attachment). Its visibility buffer may be the
+    // head's: GBufferGeneration has read that by then.
+    if (r->has_terrain) {
+        const uint64_t uses = res_mask({SOC_RES_VISIBILITY, SOC_RES_DEPTH, SOC_RES_ALBEDO, SOC_RES_NORMAL, SOC_RES_VELOCITY});
+        add_pass(r, "DrawTerrain", "Rendering G-Buffer", pre, uses, uses, [r](const soc_globals* g, hipStream_t s) {
+            const soc_frame_images& I = r->img;
+            const soc_terrain_layer& t = r->terrain;
+            return soc_draw_terrain(g, &t.mesh, t.materials, t.material_count, t.visibility, I.depth, I.albedo, I.normal,
+                                    frame_velocity(r), t.workspace, (soc_stream)s);
+        });
+    }
 }
 
 // Bloom passes of the graph (renderer.cpp:1024-1062); build_passes_tail adds the rest.
@@ -1692,6 +1724,7 @@ extern "C" int soc_renderer_set_raster_scene(soc_renderer* r, const soc_raster_s
         }
     }
     r->has_scene = scene != nullptr;
+    if (!scene) r->has_terrain = false;   // the terrain layer goes with the head it is drawn over
     r->has_draws = false;
     r->draws.clear();
     r->motion_prev = nullptr;   // a new scene turns per-object motion off (soc_renderer_set_draw_motion)
@@ -1741,6 +1774,38 @@ extern "C" int soc_renderer_set_draw_motion(soc_renderer* r, soc_transform* prev
     // the graph is not rebuilt: GBufferGeneration looks at motion_prev when it runs
     r->motion_prev = previous_transforms;
     r->motion_valid = false;
+    return SOC_OK;
+}
+
+extern "C" int soc_renderer_set_terrain(soc_renderer* r, const soc_terrain_layer* layer) {
+    const char* name = "soc_renderer_set_terrain";
+    if (!r) return set_error(SOC_E_INVALID_ARG, "%s: null renderer", name);
+    if (layer) {
+        if (!r->has_scene)
+            return set_error(SOC_E_INVALID_ARG, "%s: no raster head is set (soc_renderer_set_raster_scene / _set_draw_scene)", name);
+        const soc_mesh& m = layer->mesh;
+        if (!layer->materials || layer->material_count <= 0 || !layer->visibility || !layer->workspace || !m.positions ||
+            !m.normals || !m.uvs || !m.indices || m.vertex_count < 0 || m.triangle_count < 0)
+            return set_error(SOC_E_INVALID_ARG, "%s: incomplete layer (mesh arrays, materials, visibility, workspace)", name);
+        if (layer->shadow) {
+            if (!r->img.shadow.data) return set_error(SOC_E_INVALID_ARG, "%s: shadow pass needs images.shadow", name);
+            if (!layer->shadow_workspace)
+                return set_error(SOC_E_INVALID_ARG, "%s: shadow = 1 needs a shadow_workspace (of the shadow mesh)", name);
+            const soc_mesh& sm = layer->shadow_mesh;
+            if (sm.positions && (!sm.indices || sm.vertex_count < 0 || sm.triangle_count < 0))
+                return set_error(SOC_E_INVALID_ARG, "%s: incomplete shadow_mesh (indices, counts)", name);
+        }
+        r->terrain = *layer;
+        if (!layer->shadow_mesh.positions) r->terrain.shadow_mesh = layer->mesh;
+    }
+    r->has_terrain = layer != nullptr;
+    int rc = build_graph(r);
+    if (rc) {   // a caller's pass could not be placed beside the new passes: the graph without the layer
+        r->has_terrain = false;
+        (void)build_graph(r);
+        return rc;
+    }
+    if (r->flags & SOC_RENDERER_TIMING) return soc_renderer_set_pass_timing(r, -1, 1);
     return SOC_OK;
 }
 

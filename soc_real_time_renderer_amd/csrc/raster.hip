@@ -23,6 +23,10 @@
 // and the depth images are bit-exact against it.
 // A scene of per-entity draws with their own transforms (soc_draw_scene) runs the same triangle and pixel kernels on
 // tables built at load time, behind draw-aware versions of the two vertex kernels: see "Draw scenes" below.
+// The terrain tasks that draw over the entity tasks' images (DrawTerrainTask draw_terrain.inl, SunShadowDrawTerrainTask
+// sun_shadow_draw_terrain.inl: depth LOAD, LESS_OR_EQUAL) are a layer: the same raster kernels into a visibility buffer of
+// the layer's own (or, depth-only, into the shadow image without the clear), then the resolve's LAYER form, which
+// depth-tests each pixel against the image that is there: see "Terrain layer" below.
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -796,7 +800,15 @@ __device__ __forceinline__ VtxData fetch_vertex(const soc_mesh& mesh, const floa
 #ifndef SOC_GB_WAVES
 #define SOC_GB_WAVES 5   // waves per SIMD the resolve's registers allow: 96 VGPRs, no spill (A/B builds: 1 = unconstrained)
 #endif
-template <bool PRE>
+// LAYER = false: the resolve (GBufferGeneration). LAYER = true: the same pixel code for a layer drawn over a G-buffer that
+// is already there (soc_draw_terrain: DrawTerrain after GBufferGeneration, draw_terrain.inl: depth LOAD, LESS_OR_EQUAL,
+// three colour attachments): a pixel with an empty key, or whose fragment lies behind the depth image's value, leaves
+// before any index, vertex or texel fetch and writes nothing; a winning one writes depth, velocity, albedo and normal as
+// the resolve computes them and never the emissive image (`emissive` is not touched; the launcher passes the albedo). One
+// kernel template, not a shared __device__ function: inlined from a function, the two LAYER = false instantiations came out
+// with other registers and three more instructions; as instantiations of this template their gfx950 instructions are
+// those of the kernel before the parameter existed.
+template <bool PRE, bool LAYER>
 __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(SOC_GB_WAVES))) void gbuffer_resolve(soc_mesh mesh, const soc_material* __restrict__ mats,
                                                        const unsigned long long* __restrict__ vis, DImg depth,
                                                        DImg albedo, DImg emissive, DImg normal, DImg velocity,
@@ -829,7 +841,11 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(SOC_
     if (x >= p.width || y >= p.height) return;
     const unsigned long long key = vis[(size_t)y * p.width + x];
     const uint32_t low = (uint32_t)key;
-    if (low == KEY_EMPTY) {   // clear values (g_buffer_generation.inl:78-100, depth cleared to 1.0)
+    if (LAYER) {
+        if (low == KEY_EMPTY) return;
+        // z_t <= z_e on the float bits (both >= +0, so the bits order like the values): ties go to the layer, the later draw
+        if ((uint32_t)(key >> 32) > row_ptr<uint32_t>(depth, y)[x]) return;
+    } else if (low == KEY_EMPTY) {   // clear values (g_buffer_generation.inl:78-100, depth cleared to 1.0)
         row_ptr_w<float>(depth, y)[x] = 1.0f;
         row_ptr_w<uint2>(albedo, y)[x] = pack_h4(f4{0.2f, 0.4f, 1.0f, 1.0f});
         row_ptr_w<uint2>(emissive, y)[x] = pack_h4(f4{0.0f, 0.0f, 0.0f, 1.0f});
@@ -944,7 +960,7 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(SOC_
     const f4 al = pair ? al_pair : tex(m.albedo);
     row_ptr_w<uint2>(albedo, y)[x] = pack_h4(f4{al.x * m.albedo_factor[0] + em.x, al.y * m.albedo_factor[1] + em.y,
                                                 al.z * m.albedo_factor[2] + em.z, 1.0f});
-    row_ptr_w<uint2>(emissive, y)[x] = pack_h4(f4{em.x, em.y, em.z, 1.0f});
+    if (!LAYER) row_ptr_w<uint2>(emissive, y)[x] = pack_h4(f4{em.x, em.y, em.z, 1.0f});
     row_ptr_w<uint2>(normal, y)[x] = pack_h4(f4{n.x, n.y, n.z, 1.0f});
 }
 
@@ -1436,13 +1452,68 @@ extern "C" int soc_gbuffer_resolve(const soc_globals* g, const soc_mesh* mesh, c
         const Workspace ws = carve(workspace, mesh->vertex_count, mesh->triangle_count);
         if (mesh->vertex_count > 0)
             launch("gbuffer_vertex_setup", kWorkgroup, gbuffer_vertex_setup, ceil_div(mesh->vertex_count, 256), kWorkgroup, 0, hs(stream), *mesh, ws.vdata, p);
-        launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true>, grd, blk, 0, hs(stream), *mesh, d_materials, vis, dimg(depth), dimg(albedo),
+        launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true, false>, grd, blk, 0, hs(stream), *mesh, d_materials, vis, dimg(depth), dimg(albedo),
                                                            dimg(emissive), dimg(normal), dimg(velocity), ws.vdata, p);
     } else {
-        launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<false>, grd, blk, 0, hs(stream), *mesh, d_materials, vis, dimg(depth), dimg(albedo),
+        launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<false, false>, grd, blk, 0, hs(stream), *mesh, d_materials, vis, dimg(depth), dimg(albedo),
                                                             dimg(emissive), dimg(normal), dimg(velocity), nullptr, p);
     }
     return check_launch("gbuffer_resolve");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Terrain layer: DrawTerrain / SunShadowDrawTerrain over what the entity tasks left (soc_rt.h "Terrain layer")
+// ------------------------------------------------------------------------------------------------
+extern "C" int soc_draw_terrain(const soc_globals* g, const soc_mesh* mesh, const soc_material* d_materials,
+                                int32_t material_count, uint64_t* visibility, soc_img depth, soc_img albedo, soc_img normal,
+                                soc_img velocity, void* workspace, soc_stream stream) {
+    const char* name = "soc_draw_terrain";
+    int rc = check_mesh(mesh, name, true);
+    if (rc) return rc;
+    if (!workspace) return set_error(SOC_E_INVALID_ARG, "%s: null workspace (the layer always uses the per-vertex workspace)", name);
+    ResolveParams p{};
+    dim3 blk(64, 4), grd;
+    // DrawTerrain has no emissive attachment (draw_terrain.inl:14-17): the albedo stands in for it in the shared checks
+    rc = resolve_prepare(name, g, d_materials, material_count, visibility, depth, albedo, albedo, normal, velocity, p, grd);
+    if (rc) return rc;
+    p.wave_shape = 2;
+    grd = dim3(ceil_div(depth.width, 32), ceil_div(depth.height, 8));
+    p.model = mat4(mesh->model_matrix);
+    const float* nm = mesh->normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
+    const float n3[9] = {nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]};
+    for (int i = 0; i < 9; ++i) p.normal3.m[i] = n3[i];
+    p.triangle_count = mesh->triangle_count;
+    hipStream_t s = hs(stream);
+    const int W = depth.width, H = depth.height;
+    const size_t n = (size_t)W * H;
+    unsigned long long* vis = reinterpret_cast<unsigned long long*>(visibility);
+    launch("raster_clear_vis", kWorkgroup, raster_clear_vis, (unsigned)((n + 255) / 256), kWorkgroup, 0, s, vis, n);
+    const RasterParams rp = make_raster_params(mesh, g->camera_projection_view_matrix, W, H, SOC_CULL_FRONT);
+    rc = launch_raster(mesh, rp, visibility, (size_t)W * 8, workspace, s, "draw_terrain");
+    if (rc) return rc;
+    const Workspace ws = carve(workspace, mesh->vertex_count, mesh->triangle_count);
+    if (mesh->vertex_count > 0)
+        launch("gbuffer_vertex_setup", kWorkgroup, gbuffer_vertex_setup, ceil_div(mesh->vertex_count, 256), kWorkgroup, 0, s, *mesh, ws.vdata, p);
+    launch("gbuffer_resolve_layer", kWorkgroup, gbuffer_resolve<true, true>, grd, blk, 0, s, *mesh, d_materials, vis, dimg(depth),
+           dimg(albedo), dimg(albedo), dimg(normal), dimg(velocity), ws.vdata, p);
+    return check_launch("draw_terrain");
+}
+
+extern "C" int soc_sun_shadow_draw_terrain(const soc_mesh* mesh, const float view_projection[16], int32_t clear, soc_img depth,
+                                           void* workspace, soc_stream stream) {
+    const char* name = "soc_sun_shadow_draw_terrain";
+    int rc = check_mesh(mesh, name, false);
+    if (!rc) rc = check_img(depth, SOC_FMT_D32F, name, "depth");
+    if (rc) return rc;
+    if (!view_projection || !workspace) return set_error(SOC_E_INVALID_ARG, "%s: null view_projection or workspace", name);
+    hipStream_t s = hs(stream);
+    if (clear)   // a frame whose head draws no shadow: the clear SunShadowDraw would have made (sun_shadow_draw.inl:71-74)
+        launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)), kWorkgroup, 0, s,
+               static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
+    // sun_shadow_draw_terrain.inl:47-58: cull BACK and no depth bias (bias_constant = bias_slope = 0, as zero-initialised)
+    RasterParams p = make_raster_params(mesh, view_projection, depth.width, depth.height, SOC_CULL_BACK);
+    p.depth_only = 1;
+    return launch_raster(mesh, p, depth.data, (size_t)depth.pitch_bytes, workspace, s, "sun_shadow_draw_terrain");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1590,7 +1661,7 @@ static int resolve_draws(const char* name, const char* pass, const soc_globals* 
     else if (S > 0)
         launch("gbuffer_vertex_setup_draws", kWorkgroup, gbuffer_vertex_setup_draws, ceil_div(S, 256), kWorkgroup, 0, s, src, dw.slots,
                scene->transforms, S, ws.vdata, p);
-    launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true>, grd, blk, 0, s, view, d_materials,
+    launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true, false>, grd, blk, 0, s, view, d_materials,
            reinterpret_cast<const unsigned long long*>(visibility), dimg(depth), dimg(albedo), dimg(emissive), dimg(normal),
            dimg(velocity), ws.vdata, p);
     return check_launch(pass);

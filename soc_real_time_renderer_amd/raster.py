@@ -24,7 +24,7 @@ __all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "MATERIAL_ZERO_VELOCITY", "Me
            "normal_matrix", "materials_device", "raster_visibility", "raster_depth", "gbuffer_resolve",
            "SHADOW_BIAS_CONSTANT", "SHADOW_BIAS_SLOPE", "DrawScene", "draw", "transforms_device", "update_transforms",
            "raster_visibility_draws", "raster_depth_draws", "gbuffer_resolve_draws",
-           "gbuffer_resolve_draws_motion"]
+           "gbuffer_resolve_draws_motion", "draw_terrain", "sun_shadow_draw_terrain"]
 
 # sun_shadow_draw.inl:47-50 / :81
 SHADOW_BIAS_CONSTANT = 1.25
@@ -224,6 +224,26 @@ def gbuffer_resolve(g, mesh: MeshBuffers, d_materials: torch.Tensor, material_co
     _check(lib().soc_gbuffer_resolve(_gp(g), C.byref(mesh.struct), _ptr(d_materials), int(material_count),
                                      _ptr(visibility), img(depth), img(albedo), img(emissive), img(normal), img(velocity),
                                      _ptr(workspace), _stream(stream)), "gbuffer_resolve")
+
+
+def draw_terrain(g, mesh: MeshBuffers, d_materials: torch.Tensor, material_count: int, visibility: torch.Tensor, depth,
+                 albedo, normal, velocity, workspace: torch.Tensor, stream=None):
+    """DrawTerrain as a layer over a G-buffer that is already there (soc_draw_terrain): the mesh is rasterised into
+    `visibility` (an (H, W) buffer of its own, cleared by the call); a pixel whose terrain fragment passes
+    LESS_OR_EQUAL against `depth` gets depth, albedo, normal and velocity as gbuffer_resolve computes them, every
+    other pixel is left alone. There is no emissive image: a hidden entity's emissive stays."""
+    _check(lib().soc_draw_terrain(_gp(g), C.byref(mesh.struct), _ptr(d_materials), int(material_count), _ptr(visibility),
+                                  img(depth), img(albedo), img(normal), img(velocity), _ptr(workspace), _stream(stream)),
+           "draw_terrain")
+
+
+def sun_shadow_draw_terrain(mesh: MeshBuffers, view_projection, depth: torch.Tensor, workspace: torch.Tensor,
+                            clear: bool = False, stream=None):
+    """SunShadowDrawTerrain (soc_sun_shadow_draw_terrain): depth-only raster of the mesh into the shadow image on top
+    of what it holds (cull BACK, no depth bias); clear=True clears to 1.0 first."""
+    vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    _check(lib().soc_sun_shadow_draw_terrain(C.byref(mesh.struct), vp, int(bool(clear)), img(depth), _ptr(workspace),
+                                             _stream(stream)), "sun_shadow_draw_terrain")
 
 
 # ------------------------------------------------------------------------------------------------
