@@ -22,6 +22,9 @@ int soc_scene_mesh(int scene_id, const soc_globals* g, float* positions, float* 
 int soc_scene_material_count(int scene_id);
 int soc_scene_material_textures(int scene_id, const soc_globals* g, int size, uint8_t* rgba, float* emissive_rgb);
 int soc_scene_terrain_heightmap(int size, uint8_t* rgba);
+// test hook of the frame planner (csrc/render_execute.cpp), not in the public header
+int64_t soc_debug_plan_frame(soc_renderer* r, const soc_globals* g, int32_t phase, int32_t sky_lane_high, int32_t advance,
+                             char* buf, size_t cap);
 }
 
 namespace {
@@ -212,11 +215,19 @@ void render_graph(const soc_globals& g, int W, int H) {
         char buf[4096];
         expect(soc_renderer_metrics_json(r, 0, buf, sizeof buf) > 0, "metrics json");
         expect(soc_renderer_metrics_json(r, 0, buf, 8) > 8, "metrics json truncated");
+        // the frame planner through its test hook (no GPU call): the first one-call frame over the raster head and the
+        // caller passes and the frame after it, then a frame split into its two phases
+        char plan[8192];
+        for (int k = 0; k < 2; ++k)
+            expect(soc_debug_plan_frame(r, &g, SOC_PHASE_ALL, k, 1, plan, sizeof plan) > 0, "plan: one-call frame");
+        expect(std::strstr(plan, "run\tGBufferGeneration\t0\t") != nullptr, "plan: runs the raster head");
+        expect(soc_debug_plan_frame(r, &g, SOC_PHASE_PRE_EXPOSURE, 0, 1, plan, 16) > 16, "plan: PRE phase, truncated");
+        expect(soc_debug_plan_frame(r, &g, SOC_PHASE_POST_EXPOSURE, 0, 0, nullptr, 0) > 0, "plan: POST phase, length only");
+        expect(soc_debug_plan_frame(r, nullptr, SOC_PHASE_ALL, 0, 0, plan, sizeof plan) < 0, "plan: null globals rejected");
         expect(soc_renderer_set_raster_scene(r, nullptr) == SOC_OK, "clear raster scene");
         expect(soc_renderer_set_exposure_pixels(r, (uint64_t)W * H * 8, 1) == SOC_OK, "exposure pixels");
         soc_renderer_destroy(r);
     }
-    (void)g;
 }
 
 void writers(int W, int H) {
