@@ -324,6 +324,9 @@ DEBUG_FUNCTIONS = {
     "soc_debug_bloom_generic": (_I, [C.c_int32, _IMG, _IMG, _P]),
     "soc_debug_draw_motion": (_I, [_P]),
     "soc_debug_plan_frame": (C.c_int64, [_P, _G, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "soc_debug_plan_clouds": (C.c_int64, [_G, _IMG, _IMG, _IMG, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_char_p,
+                                          C.c_size_t]),
+    "soc_debug_cloud_state_bytes": (C.c_size_t, []),
     "soc_debug_bloom_zero_cell_footprint": (None, [C.c_int32] * 4 + [C.POINTER(C.c_int32)]),
 }
 

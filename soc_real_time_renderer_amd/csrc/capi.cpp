@@ -3,6 +3,7 @@
 // render_graph.cpp, the frame scheduler render_execute.cpp.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -50,7 +51,10 @@ std::mutex g_knob_mu;
 // the environment's value of each knob read so far: (name, (set, value)); a knob that is not set returns the caller's
 // default on every call (the default may differ between callers, e.g. per renderer flags)
 std::vector<std::pair<std::string, std::pair<bool, int>>> g_knobs;
+std::atomic<uint32_t> g_knob_generation{1};   // soc_tuning_reload calls so far, plus one
 }  // namespace
+
+uint32_t tuning_generation() { return g_knob_generation.load(std::memory_order_acquire); }
 
 int tuning_knob(const char* name, int dflt) {
     std::lock_guard<std::mutex> lock(g_knob_mu);
@@ -194,4 +198,5 @@ extern "C" const char* soc_device_arch(void) { return "gfx950"; }
 extern "C" void soc_tuning_reload(void) {
     std::lock_guard<std::mutex> lock(g_knob_mu);
     g_knobs.clear();
+    g_knob_generation.fetch_add(1, std::memory_order_release);
 }

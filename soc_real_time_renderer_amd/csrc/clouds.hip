@@ -11,7 +11,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "soc_internal.hpp"
+#include "clouds_plan.hpp"
 
 // Profiling builds only (tools/kernel_variants.py): 1 = atmosphere only, 2 = cloud march only,
 // 3 = cloud march without the sun-visibility march, 4 = classify only, 5 = classify only without the
@@ -61,29 +61,9 @@ __device__ __forceinline__ float cl_rcp(float x) {
     else return __builtin_amdgcn_rcpf(x);
 }
 
-constexpr int kNoise = 64, kNoiseMask = 63;
-// LDS quad table: 81 x 81 entries (64 + the 17-texel tap offset), so the second tap of get_3d_noise is
-// the first tap's address plus a constant (an immediate ds_read offset) with no wrap arithmetic.
-constexpr int kTap2 = 17, kTW = kNoise + kTap2, kTable = kTW * kTW;
-// the quad tables padded to whole 16-B chunks (prebuilt in the workspace by clouds_od_lut, copied into LDS)
-constexpr int kTableU32 = (kTable + 3) & ~3, kTableU2 = (kTable + 1) & ~1;
-// the row table (RowF): one f16 pair per texel position of 82 rows (a quad's bottom row is the next row's entry)
-constexpr int kRowTable = (kTW + 1) * kTW, kRowU32 = (kRowTable + 3) & ~3;
-constexpr int kTableBuild = kRowU32 > kTableU32 ? kRowU32 : kTableU32;   // entries clouds_od_lut builds
 constexpr float kEarthRadius = 6371000.0f, kMinH = 1600.0f, kMaxH = 500.0f + 1600.0f, kSunBrightness = 3.0f;
 constexpr float kPi = 3.14159265358979f;   // acos(-1.0) in fp32
 constexpr float kLn2 = 0.693147182f;       // log(2.0) in fp32
-
-struct CloudParams {
-    Mat4 inv_proj, inv_view;
-    float sun[3];      // -sun_info.direction
-    float cam[3];
-    float res_x_m1, res_y_m1;  // resolution - 1
-    float r_res_x_m1, r_res_y_m1;  // recip_rn(resolution - 1) for the ray uv x / (W - 1) (div_rn)
-    float elapsed;
-    float sun_factor;  // max(min(|sun.x|, |sun.z|) + sun.y, 0)
-    int res_x, res_y;
-};
 
 // Q = uint32_t: LDS quads of 4 bytes (c0 c1 / c2 c3), filtered in integers (v_dot2_u32_u16); Q = uint2: the same quad
 // in float form, two f16 pairs (256 c0 | (c1 - c0) << 16, 256 c2 | (c3 - c2) << 16) filtered by v_fma_mix_f32 (twice
@@ -521,7 +501,7 @@ __device__ f3 volumetric_clouds(const Ctx& cx, f3 dir, f3 sun, f3 color, float d
 }
 
 // atmosphere, :353-439 (primary ray starts at iTime = elapsed_time: quirk Q10)
-constexpr float kRPlanet = 6371e3f, kRAtmos = 6471e3f, kShRlh = 8e3f, kShMie = 1.2e3f;
+constexpr float kRAtmos = 6471e3f, kShRlh = 8e3f, kShMie = 1.2e3f;
 constexpr float kExpR = -1.44269504f / kShRlh, kExpM = -1.44269504f / kShMie;   // exp(-h/sh) = exp2(h * kExp)
 
 // The secondary (sun) ray of a primary sample, :399-423: its (Rayleigh, Mie) optical depth. It depends on the sample
@@ -566,12 +546,7 @@ __device__ __forceinline__ f2v secondary_od(float A, float PoD, float C2) {
 // finite (a sun ray through the planet, whose attenuation the reference takes to 0) are stored as NaN, and samples that
 // read one march their secondary ray as before. SOC_CLOUDS_OD_LUT=0 marches every secondary ray (the single-lane kernel
 // always does).
-constexpr int kOdR = 256, kOdM = 512;
 constexpr float kOdRScale = (float)(kOdR - 1) / (kRAtmos - kRPlanet), kOdMScale = (float)(kOdM - 1) * 0.5f;
-struct OdLut {
-    const float2* t;   // [kOdR][kOdM] (log2 odR, log2 odM); nullptr: no table
-    float C2;
-};
 
 // Entry i of the quad tables stage_noise / stage_noise_wide build (the same bytes).
 template <bool NOISE_R8>
@@ -714,12 +689,6 @@ __device__ f3 atmosphere(f3 r, f3 r0, f3 pSun, float iTime, const OdLut& L) {
 // discriminant rsi computes, interpolates (totalRlh, totalMie) bilinearly and applies its exact phase functions. Against
 // evaluating every pixel (float64 study over the C3 / C4 view frusta, tools/sky_table_check.py): at most 0.04 RGBA8
 // levels. SOC_CLOUDS_SKY_TABLE=0 evaluates every pixel (the single-lane kernel always does).
-constexpr int kSvT = 128, kSvU = 64, kSvEntries = 3 * kSvT * kSvU;
-struct SkyTab {
-    const float4* t;   // [3][kSvT][kSvU] x 2: (totalRlh.xyz, totalMie.x), (totalMie.yz, -, -); nullptr: no table
-    float upx, upy, upz, shx, shy, shz, btx, bty, btz;   // frame: up = r0 / |r0|, the sun's horizontal direction, up x sh
-    float eh, dl;
-};
 __device__ __forceinline__ f3 sv_dir(const SkyTab& st, int b, float t, float u) {
     const float eh = st.eh, dl = st.dl;
     const float e = b == 0 ? -(eh + dl) - t * t * (1.0f - eh - dl)
@@ -768,8 +737,6 @@ __device__ f3 atmosphere_table(f3 r, f3 r0, f3 pSun, const SkyTab& st) {
     const float4 v0 = lerp4(a0, b0, wt), v1 = lerp4(a1, b1, wt);
     return atmosphere_phase(r, pSun, f3{v0.x, v0.y, v0.z}, f3{v0.w, v1.x, v1.y});
 }
-
-constexpr int TX = 16, TY = 16;
 
 // View ray of pixel (x, y): main(), :445-452 (ray_uv = pixel / (resolution - 1), not texel centres).
 __device__ __forceinline__ f3 sky_dir(const CloudParams& p, int x, int y) {
@@ -899,7 +866,6 @@ __global__ __launch_bounds__(kWorkgroup) void clouds_kernel(DImg depth, DImg noi
 // kClassifyTiles 64x16 tiles stacked vertically per workgroup (a 64x64 region): one list atomic per region instead of per
 // tile. The atomics on the one counter serialise across the XCDs: at one per 64x16 tile they cost C4 34 of its 59 us
 // (profiles/r04_probe_clouds_classify.txt).
-constexpr int kClassifyTiles = 4;
 // HOIST: every tile's depth samples issued before the first tile's stores (one memory round trip instead of four; the
 // same samples). Faster alone (C3 299 -> 291 us, C4 541 -> 504 us CloudRendering) but in the frame only where the sky
 // lane is the critical path (C4 +1.8 %; C3 -1.1 %, C2 -1 %: profiles/r05_ab_clouds_classify_hoist.txt), so the render
@@ -1031,34 +997,8 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(8)))
 // Every position is re-derived with the same additions (cp = inc*dither + start, += inc), so od and vis
 // are the bits the single-lane march computes. A workgroup whose pairs do not fit the list marks its
 // pixels for the single-lane march in resolve.
-constexpr int kShards = 8;
-// clouds_sunvis workgroup: 512 lanes (the 26 KiB noise table caps residency at 6 workgroups per CU: 512 lanes give the
-// full 8 waves per SIMD); its launch bound
-constexpr uint32_t kSunvisLanes = 512;
 constexpr uint32_t kInline = 0x80000000u;   // pix_mask flag: march this pixel in resolve
 
-struct PairBufs {
-    uint32_t* counts;     // [kShards] pair counts (workspace counter block)
-    uint32_t* pairs;      // [kShards * cap] (list index << 5) | step
-    float* od;            // [kShards * cap] od of each pair's step (clouds_density)
-    float* vis;           // [kShards * cap] sun visibility of each pair's step (clouds_sunvis); od and vis in two dense
-                          // arrays (round 5: one float2 array took each kernel's 4-byte writes at an 8-byte stride, so
-                          // every written line was half written)
-    uint32_t* pix_mask;   // [W*H] per list entry: dense-step mask | kInline
-    uint32_t* batch_base; // [W*H/256] per 256-entry batch: physical index of its first pair | kInline
-    float4* geom;         // [W*H] x 2 per list entry: (start, dither), (inc, stepLength) of its march (density
-                          // writes it for upward rays when store_geom; sunvis and resolve read it instead of re-deriving
-                          // it; store_geom == 0: they re-derive it from the list entry, the same bits)
-    float* od_tmp;        // [od_blocks][24][256]: per density workgroup, the od of its current batch's dense steps until
-                          // their pair slots are known; density then stores od in od[slot], and sunvis only adds vis
-    const uint32_t* noise_quads;  // [kTableU32] the frame's noise quad table (clouds_od_lut), or nullptr: stage_noise
-    const uint2* noise_wide;      // [kTableU2] the same quads in float form (stage_noise_wide)
-    const uint32_t* noise_rows;   // [kRowU32] the row table (stage_noise_rows)
-    uint32_t store_geom;  // tuning knob SOC_CLOUDS_GEOM
-    uint32_t od_blocks;   // density workgroups the od scratch holds (the density grid is clamped to it)
-    uint32_t n;           // list capacity (W*H)
-    uint32_t cap;         // pairs per shard
-};
 
 
 
@@ -1428,370 +1368,126 @@ int resident_blocks(K kernel, int threads = 256) {
     return per_cu * cus;
 }
 
-}  // namespace
-}  // namespace soc
 
-using namespace soc;
+// The instantiation of each kernel. With this compiler the device code is emitted in the order in which the host code
+// first names each instantiation (observed; profiles/clouds_plan_isa_identity.txt), so they are named here in the order
+// the launcher had before it was split: the two-way picks, the six residency queries, the atmosphere's table form, then
+// the march kernels of the R8 noise before the RGBA8's. That is why cloud_residency() sits between the picks.
+auto single_kernel(bool r8) { return r8 ? clouds_kernel<true> : clouds_kernel<false>; }
+auto od_lut_kernel(bool r8) { return r8 ? clouds_od_lut<true> : clouds_od_lut<false>; }
+auto classify_kernel(bool hoist) { return hoist ? clouds_classify<true> : clouds_classify<false>; }
 
-namespace {
-// Workspace: counters (256 B: [0] sky pixels, [8..15] pair counts per shard) | sky list (u32) |
-// atmosphere (float4) | per-pixel dense mask (u32) | per-batch first pair (u32) | march geometry (2 float4) | pairs (u32) |
-// od per pair (float) | vis per pair (float) | od scratch of the density workgroups (24 x 256 float each, at most kDensityBlocks) |
-// the secondary-ray optical-depth table (kOdR x kOdM float2, 1 MiB) | sky-view table | noise tables |
-// the second counter block (256 B).
-// Pair capacity 2 per pixel of the image (8 shards).
-// Per 256-entry batch of the list: the physical index of its first pair (or kInline).
-// density workgroups the od scratch is sized for: the resident set (6 per CU on 256 CUs is 1536) times the largest grid
-// multiplier used (2: a sky-bound frame's density grid), 24 KiB each (4096 held 48 MiB more than any grid uses)
-constexpr size_t kDensityBlocks = 3072;
-struct CloudWs {
-    uint32_t* counter;
-    uint32_t* list;
-    float4* atmos;
-    PairBufs pb;
-    float2* od_lut;   // secondary-ray optical-depth table (kOdR x kOdM)
-    uint32_t* noise_quads;   // [kTableU32] noise quad tables (clouds_od_lut)
-    uint2* noise_wide;       // [kTableU2]
-    uint32_t* noise_rows;    // [kRowU32]
-    float4* sky_tab;  // sky-view table (kSvEntries x 2 float4)
-    uint32_t* counter_b;     // the second counter block (a renderer's frames alternate between the two)
-    size_t bytes;
+// The resident sets the grids are sized by: queried once, of these six instantiations.
+const CloudResidency& cloud_residency() {
+    static const CloudResidency res = [] {
+        return CloudResidency{resident_blocks(clouds_atmosphere<false>),
+                              resident_blocks(clouds_density<false>),
+                              resident_blocks(clouds_sunvis<false, kSunvisLanes, true>, kSunvisLanes),
+                              resident_blocks(clouds_sunvis<false, kSunvisLanes, false, true>, kSunvisLanes),
+                              resident_blocks(clouds_sunvis<false, kSunvisLanes, false, true, true>, kSunvisLanes),
+                              resident_blocks(clouds_resolve<false, true>)};
+    }();
+    return res;
+}
+
+auto atmosphere_kernel(bool table) { return table ? clouds_atmosphere<true> : clouds_atmosphere<false>; }
+
+// The march kernels by [noise is R8][form]: each form of clouds_plan.hpp by name (the hook's text in clouds_plan.cpp
+// names them the same way, so neither depends on the enumerators' order).
+struct MarchKernels {
+    decltype(&clouds_density<true>) density[kDensityForms];
+    decltype(&clouds_sunvis<true, kSunvisLanes>) sunvis[kSunvisForms];
+    decltype(&clouds_resolve<true>) resolve[kResolveForms];
 };
-CloudWs cloud_ws_layout(void* base, size_t n) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    char* b = static_cast<char*>(base);
-    CloudWs w;
-    size_t off = 256;
-    w.counter = reinterpret_cast<uint32_t*>(b);
-    w.list = reinterpret_cast<uint32_t*>(b + off);
-    off = al(off + n * 4);
-    w.atmos = reinterpret_cast<float4*>(b + off);
-    off = al(off + n * 16);
-    w.pb.counts = w.counter + 8;
-    w.pb.pix_mask = reinterpret_cast<uint32_t*>(b + off);
-    off = al(off + n * 4);
-    w.pb.batch_base = reinterpret_cast<uint32_t*>(b + off);
-    off = al(off + (n / 256 + 1) * 4);
-    w.pb.geom = reinterpret_cast<float4*>(b + off);
-    off = al(off + n * 32);
-    w.pb.cap = (uint32_t)((2 * n + kShards - 1) / kShards);
-    w.pb.pairs = reinterpret_cast<uint32_t*>(b + off);
-    off = al(off + (size_t)kShards * w.pb.cap * 4);
-    w.pb.od = reinterpret_cast<float*>(b + off);
-    off = al(off + (size_t)kShards * w.pb.cap * 4);
-    w.pb.vis = reinterpret_cast<float*>(b + off);
-    off = al(off + (size_t)kShards * w.pb.cap * 4);
-    w.pb.od_tmp = reinterpret_cast<float*>(b + off);
-    w.pb.od_blocks = (uint32_t)std::min<size_t>(kDensityBlocks, (n + 255) / 256);
-    w.pb.n = (uint32_t)n;
-    off = al(off + (size_t)w.pb.od_blocks * 24 * 256 * 4);
-    w.od_lut = reinterpret_cast<float2*>(b + off);
-    off = al(off + (size_t)kOdR * kOdM * sizeof(float2));
-    w.sky_tab = reinterpret_cast<float4*>(b + off);
-    off = al(off + (size_t)kSvEntries * 2 * sizeof(float4));
-    w.noise_quads = reinterpret_cast<uint32_t*>(b + off);
-    off = al(off + (size_t)kTableU32 * 4);
-    w.noise_wide = reinterpret_cast<uint2*>(b + off);
-    off = al(off + (size_t)kTableU2 * 8);
-    w.noise_rows = reinterpret_cast<uint32_t*>(b + off);
-    off = al(off + (size_t)kRowU32 * 4);
-    w.counter_b = reinterpret_cast<uint32_t*>(b + off);
-    off += 256;
-    w.bytes = off;
-    return w;
+template <bool R8>
+constexpr MarchKernels march_kernels() {
+    MarchKernels k{};
+    k.density[kDensityRows] = clouds_density<R8, 8, true>;
+    k.density[kDensityBatch4] = clouds_density<R8, 4>;
+    k.density[kDensityBatch8] = clouds_density<R8, 8>;
+    k.density[kDensityBatch1] = clouds_density<R8>;
+    k.sunvis[kSunvisRows] = clouds_sunvis<R8, kSunvisLanes, false, true, true>;
+    k.sunvis[kSunvisQuads] = clouds_sunvis<R8, kSunvisLanes, false, true>;
+    k.sunvis[kSunvisWidePf] = clouds_sunvis<R8, kSunvisLanes, true, true>;
+    k.sunvis[kSunvisWide] = clouds_sunvis<R8, kSunvisLanes, true>;
+    k.resolve[kResolveFold4] = clouds_resolve<R8, true, 4>;
+    k.resolve[kResolveFold8] = clouds_resolve<R8, true, 8>;
+    k.resolve[kResolveFold1] = clouds_resolve<R8, true>;
+    k.resolve[kResolveAtmos] = clouds_resolve<R8, false>;
+    return k;
 }
+template <bool R8>
+constexpr MarchKernels kMarchKernels = march_kernels<R8>();
+
+// Issues what plan_clouds decided, in order.
+int issue_clouds(const CloudPlan& pl, const soc_img& depth, const soc_img& noise, const soc_img& target, hipStream_t s) {
+    if (!pl.launch) return SOC_OK;
+    const CloudParams& p = pl.p;
+    const DImg nz = dimg(noise);
+    if (pl.single) {
+        launch("clouds_kernel", kWorkgroup, single_kernel(pl.r8), dim3(pl.single_gx, pl.single_gy),
+               dim3(TX, TY), 0, s, dimg(depth), nz, dimg(target), p);
+        return check_launch("cloud_rendering");
+    }
+    const CloudWs& ws = pl.ws;
+    const MarchKernels& march = pl.r8 ? kMarchKernels<true> : kMarchKernels<false>;
+    uint32_t* const block[2] = {ws.counter, ws.counter_b};
+    uint32_t* counter = block[pl.counter_block];
+    uint32_t* list = ws.list;
+    if (pl.prime_blocks &&
+        (hipMemsetAsync(ws.counter, 0, 256, s) != hipSuccess || hipMemsetAsync(ws.counter_b, 0, 256, s) != hipSuccess))
+        return set_error(SOC_E_HIP, "soc_cloud_rendering: counter block clear failed");
+    if (pl.build_tables)
+        launch("clouds_od_lut", kWorkgroup, od_lut_kernel(pl.r8), pl.lut_grid, kWorkgroup, 0, s,
+               pl.build_od ? ws.od_lut : nullptr, pl.C2, counter, pl.lut_blocks, nz, ws.noise_quads, ws.noise_wide, ws.noise_rows);
+    launch("clouds_classify", kWorkgroup, classify_kernel(pl.hoist),
+           dim3(pl.classify_gx, pl.classify_gy), kWorkgroup, 0, s, dimg(depth), dimg(target), p, pl.vec_store, counter, list,
+           pl.zero_block < 0 ? nullptr : block[pl.zero_block]);
+    if (pl.classify_only) return check_launch("cloud_rendering");
+    if (pl.sky_table)
+        launch("clouds_sky_table", kWorkgroup, clouds_sky_table, ceil_div(kSvEntries, kWorkgroup), kWorkgroup, 0, s, ws.sky_tab, p,
+               pl.st, pl.lut);
+    auto atmos = [&](int pos) {
+        if (pl.atmos_pos != pos || pl.fold) return;
+        launch("clouds_atmosphere", kWorkgroup, atmosphere_kernel(pl.sky_table), pl.atmos_grid,
+               kWorkgroup, 0, s, p, counter, list, ws.atmos, pl.lut, pl.st);
+    };
+    atmos(0);
+    launch("clouds_density", kWorkgroup, march.density[pl.density], pl.density_grid, kWorkgroup, 0, s, nz, p, counter,
+           list, ws.pb);
+    atmos(1);
+    launch("clouds_sunvis", kSunvisLanes, march.sunvis[pl.sunvis], pl.sunvis_grid, kSunvisLanes, 0, s, nz, p, list, ws.pb);
+    atmos(2);
+    launch("clouds_resolve", kWorkgroup, march.resolve[pl.resolve], pl.resolve_grid, kWorkgroup, 0, s, nz, dimg(target),
+           p, counter, list, ws.atmos, ws.pb, pl.st);
+    return check_launch("cloud_rendering");
+}
+
 }  // namespace
 
-extern "C" size_t soc_cloud_rendering_workspace_size(int32_t width, int32_t height) {
-    if (width <= 0 || height <= 0) return 0;
-    return cloud_ws_layout(nullptr, (size_t)width * (size_t)height).bytes;
-}
-
-extern "C" int soc_cloud_rendering(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
-                                   soc_stream stream) {
-    return soc::cloud_rendering_launch(g, depth, noise, target, workspace, stream, false);
-}
-
-namespace {
-int cloud_rendering_queue(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
-                          soc_stream stream, bool sky_bound, CloudState* state);
-}
-int soc::cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
-                                soc_stream stream, bool sky_bound, CloudState* state) {
-    const int rc = cloud_rendering_queue(g, depth, noise, target, workspace, stream, sky_bound, state);
-    if (rc && state) {   // a frame that was not queued whole: the blocks are cleared anew, the tables rebuilt
+int cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
+                           soc_stream stream, bool sky_bound, CloudState* state) {
+    CloudPlan plan;
+    int rc = plan_clouds(g, depth, noise, target, workspace, sky_bound, SOC_CLOUDS_PROFILE, cloud_residency(), state, plan);
+    if (!rc) rc = issue_clouds(plan, depth, noise, target, hs(stream));
+    // a frame that was not queued whole: the blocks are cleared anew, the tables rebuilt. (The planner has already marked
+    // the blocks primed, recorded the keys and advanced `frame`; only the frame's parity survives this reset, and both
+    // blocks are cleared before either is used again.)
+    if (rc && state) {
         state->blocks_primed = false;
         state->invalidate_tables();
     }
     return rc;
 }
 
-namespace {
-int cloud_rendering_queue(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
-                          soc_stream stream, bool sky_bound, CloudState* state) {
-    static const char* P = "soc_cloud_rendering";
-    if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
-    int rc = check_img(depth, SOC_FMT_D32F, P, "depth");
-    if (!rc) rc = check_img(target, SOC_FMT_RGBA8_UNORM, P, "target");
-    if (!rc) rc = check_img(noise, 0, P, "noise");
-    if (rc) return rc;
-    if (noise.format != SOC_FMT_R8_UNORM && noise.format != SOC_FMT_RGBA8_UNORM)
-        return set_error(SOC_E_UNSUPPORTED, "%s: noise must be R8_UNORM or RGBA8_UNORM", P);
-    if (noise.width != 64 || noise.height != 64)
-        return set_error(SOC_E_SHAPE, "%s: noise texture must be 64x64 (assets/Clouds/noise.png)", P);
-    CloudParams p;
-    p.inv_proj = mat4(g->camera_inverse_projection_matrix);
-    p.inv_view = mat4(g->camera_inverse_view_matrix);
-    for (int i = 0; i < 3; ++i) {
-        p.sun[i] = -g->sun_info.direction[i];
-        p.cam[i] = g->camera_position[i];
-    }
-    p.res_x = g->resolution[0];
-    p.res_y = g->resolution[1];
-    p.res_x_m1 = (float)g->resolution[0] - 1.0f;
-    p.res_y_m1 = (float)g->resolution[1] - 1.0f;
-    p.r_res_x_m1 = recip_rn(g->resolution[0] - 1);
-    p.r_res_y_m1 = recip_rn(g->resolution[1] - 1);
-    p.elapsed = g->elapsed_time;
-    p.sun_factor = fmaxf(fminf(fabsf(p.sun[0]), fabsf(p.sun[2])) + p.sun[1], 0.0f);
-    const int W = std::min(target.width, p.res_x), H = std::min(target.height, p.res_y);
-    if (W <= 0 || H <= 0) return SOC_OK;
-    if (W > 65535 || H > 65535) return set_error(SOC_E_SHAPE, "%s: extent above 65535", P);
-    hipStream_t s = hs(stream);
-    const bool r8 = noise.format == SOC_FMT_R8_UNORM;
-    if (!workspace) {
-        dim3 blk(TX, TY), grd(ceil_div(W, TX), ceil_div(H, TY));
-        if (r8) launch("clouds_kernel", kWorkgroup, clouds_kernel<true>, grd, blk, 0, s, dimg(depth), dimg(noise), dimg(target), p);
-        else launch("clouds_kernel", kWorkgroup, clouds_kernel<false>, grd, blk, 0, s, dimg(depth), dimg(noise), dimg(target), p);
-        return check_launch("cloud_rendering");
-    }
-    // the caller sized the workspace for the target extent (soc_cloud_rendering_workspace_size)
-    CloudWs ws = cloud_ws_layout(workspace, (size_t)target.width * (size_t)target.height);
-    ws.pb.store_geom = (uint32_t)tuning_knob("SOC_CLOUDS_GEOM", 1);
-    uint32_t* list = ws.list;
-    // the secondary-ray table (SOC_CLOUDS_OD_LUT=0: march every secondary ray, the single-lane kernel's bits) and the
-    // noise quad tables (SOC_CLOUDS_NOISE_TABLE=0: each march workgroup stages them from the noise image texel by texel,
-    // the same bytes), both built by clouds_od_lut.
-    // Stateless (no `state`, soc_cloud_rendering; or SOC_CLOUDS_STATIC_TABLES=0): built on every call, by the kernel that
-    // also clears the call's counter block (block 0).
-    // A renderer's frames (`state`): both are static in real use (the od table depends only on C2 = dot(pSun, pSun), which
-    // changes when the sun is edited; the noise is an asset loaded once), so each is built when first needed and again
-    // only when its key changes (the bit pattern of C2; the noise image's data, format, pitch;
-    // soc_renderer_invalidate_cloud_tables for texels rewritten in place). The counter block then has no launch to clear
-    // it: frame N counts in block N & 1, and one workgroup of its clouds_classify clears block (N + 1) & 1, which frame
-    // N - 1 used last (all its kernels precede this frame's in stream order); both blocks are cleared when the renderer
-    // first uses the workspace this way. The classification runs over the whole image in every frame, so a frame
-    // without sky clears the next block too, and a sky frame after it starts from zero. (Not clouds_density: one more
-    // kernel argument took its scratch from 12 to 32 B per lane, +4.5 us at C3 and C4.)
-    OdLut lut{nullptr, 0.0f};
-    const bool use_lut = SOC_CLOUDS_PROFILE < 4 && tuning_knob("SOC_CLOUDS_OD_LUT", 1);
-    const bool noise_tab = tuning_knob("SOC_CLOUDS_NOISE_TABLE", 1) != 0;
-    const float C2 = p.sun[0] * p.sun[0] + p.sun[1] * p.sun[1] + p.sun[2] * p.sun[2];   // dot3(pSun, pSun)
-    if (use_lut) lut = OdLut{ws.od_lut, C2};
-    ws.pb.noise_quads = noise_tab ? ws.noise_quads : nullptr;
-    ws.pb.noise_wide = noise_tab ? ws.noise_wide : nullptr;
-    ws.pb.noise_rows = noise_tab ? ws.noise_rows : nullptr;
-    // SOC_CLOUDS_STATIC_TABLES: 1 the static form, 0 the per-call build, default (-1) the static form except in a
-    // sky-bound frame above 1440p (the render graph's high-priority sky lane, as the atmosphere's position below): the
-    // C4 frame at 3840x2160 is 0.5 % slower without the 13 us build launch ahead of the classification (1498-1504 fps
-    // against 1506-1511 with it, five alternating runs: the lane's kernels start earlier, and clouds_sunvis then runs
-    // 12 us longer beside the main lane), while the sky-bound C2 frame at 1920x1080 gains 3 % and C3 1.5 %
-    // (profiles/r07_ab_static_tables.txt). The same bits in every form.
-    const int static_knob = tuning_knob("SOC_CLOUDS_STATIC_TABLES", -1);
-    const bool static_tables = static_knob >= 0 ? static_knob != 0 : !(sky_bound && (long long)W * H > 2560LL * 1440LL);
-    const bool cached = state && SOC_CLOUDS_PROFILE < 4 && static_tables;
-    uint32_t* counter = ws.counter;
-    uint32_t* zero_next = nullptr;
-    bool build_od = use_lut, build_noise = noise_tab;
-    if (cached) {
-        if (state->workspace != workspace) {   // another workspace: nothing of the record holds
-            state->invalidate_tables();
-            state->blocks_primed = false;
-            state->workspace = workspace;
-        }
-        if (!state->blocks_primed) {
-            if (hipMemsetAsync(ws.counter, 0, 256, s) != hipSuccess || hipMemsetAsync(ws.counter_b, 0, 256, s) != hipSuccess)
-                return set_error(SOC_E_HIP, "%s: counter block clear failed", P);
-            state->blocks_primed = true;
-        }
-        uint32_t c2_bits;
-        memcpy(&c2_bits, &C2, sizeof c2_bits);
-        if (state->od_valid && state->c2_bits != c2_bits) state->od_valid = false;
-        if (state->noise_valid && (state->noise_data != noise.data || state->noise_format != noise.format ||
-                                   state->noise_pitch != noise.pitch_bytes))
-            state->noise_valid = false;
-        build_od = use_lut && !state->od_valid;
-        build_noise = noise_tab && !state->noise_valid;
-        if (build_od) {
-            state->od_valid = true;
-            state->c2_bits = c2_bits;
-        }
-        if (build_noise) {
-            state->noise_valid = true;
-            state->noise_data = noise.data;
-            state->noise_format = noise.format;
-            state->noise_pitch = noise.pitch_bytes;
-        }
-        counter = (state->frame & 1u) ? ws.counter_b : ws.counter;
-        zero_next = (state->frame & 1u) ? ws.counter : ws.counter_b;
-        state->frame++;
-    } else if (state) {   // the per-call form leaves the blocks and the tables as any caller of the workspace would
-        state->invalidate_tables();
-        state->blocks_primed = false;
-        state->workspace = nullptr;
-    }
-    ws.pb.counts = counter + 8;
-    if (!cached || build_od || build_noise) {
-        // blocks [0, lut_blocks) build the od table (without it: one block, which only clears the counter block), the
-        // blocks after them the noise tables. The cached form's block is already clear; the kernel clears it again.
-        const int lut_blocks = build_od ? ceil_div(kOdR * kOdM, kWorkgroup) : 1;
-        const int blocks_all = lut_blocks + (build_noise ? ceil_div(kTableBuild, kWorkgroup) : 0);
-        float2* lt = build_od ? ws.od_lut : nullptr;
-        if (noise.format == SOC_FMT_R8_UNORM)
-            launch("clouds_od_lut", kWorkgroup, clouds_od_lut<true>, blocks_all, kWorkgroup, 0, s, lt, C2, counter, lut_blocks,
-                   dimg(noise), ws.noise_quads, ws.noise_wide, ws.noise_rows);
-        else
-            launch("clouds_od_lut", kWorkgroup, clouds_od_lut<false>, blocks_all, kWorkgroup, 0, s, lt, C2, counter, lut_blocks,
-                   dimg(noise), ws.noise_quads, ws.noise_wide, ws.noise_rows);
-    }
-    const int vec_store = (target.pitch_bytes % 16 == 0) && (reinterpret_cast<uintptr_t>(target.data) % 16 == 0);
-    const bool hoist = sky_bound || tuning_knob("SOC_CLOUDS_CLASSIFY_HOIST", 0);
-    if (hoist)
-        launch("clouds_classify", kWorkgroup, clouds_classify<true>, dim3(ceil_div(W, 64), ceil_div(H, 16 * kClassifyTiles)),
-               kWorkgroup, 0, s, dimg(depth), dimg(target), p, vec_store, counter, list, zero_next);
-    else
-        launch("clouds_classify", kWorkgroup, clouds_classify<false>, dim3(ceil_div(W, 64), ceil_div(H, 16 * kClassifyTiles)),
-               kWorkgroup, 0, s, dimg(depth), dimg(target), p, vec_store, counter, list, zero_next);
-    // One resident wave set per kernel, grid-stride over the list / pairs: the long per-item work is
-    // balanced over all SIMDs instead of running as a second, partially filled round.
-    static int res_atmos = 0, res_density = 0, res_sunvis = 0, res_sunvis_n = 0, res_sunvis_r = 0, res_resolve = 0;
-    if (!res_atmos) {
-        res_atmos = resident_blocks(clouds_atmosphere<false>);
-        res_density = resident_blocks(clouds_density<false>);
-        res_sunvis = resident_blocks(clouds_sunvis<false, kSunvisLanes, true>, kSunvisLanes);
-        res_sunvis_n = resident_blocks(clouds_sunvis<false, kSunvisLanes, false, true>, kSunvisLanes);
-        res_sunvis_r = resident_blocks(clouds_sunvis<false, kSunvisLanes, false, true, true>, kSunvisLanes);
-        res_resolve = resident_blocks(clouds_resolve<false, true>);
-    }
-    const long long blocks = ((long long)W * H + 255) / 256;
-    if (SOC_CLOUDS_PROFILE >= 4) return check_launch("cloud_rendering");
-    // SOC_CLOUDS_GRID_MULT: the sun-visibility and resolve grids as this many times the resident wave set (1: one
-    // persistent set; more: workgroups queue behind each other, so the dispatcher can place the main lane's workgroups
-    // between them instead of on what a persistent set leaves). The same bits at any grid. Default 2: C3 1678 -> 1699 fps,
-    // C2 5313 -> 5526, C4 unchanged; 3 measured C3 1644, C4 1342; 4 / 8: C3 1646 / 1629 (profiles/r05_ab_clouds_grid_mult.txt).
-    const int gmul = std::max(1, tuning_knob("SOC_CLOUDS_GRID_MULT", 2));
-    auto grid = [&](int res, long long items_blocks) { return (int)std::max(1LL, std::min<long long>(res, items_blocks)); };
-    auto grid_m = [&](int res, long long items_blocks) {
-        return (int)std::max(1LL, std::min<long long>((long long)res * gmul, items_blocks));
-    };
-    // Position of the atmosphere kernel in the lane (it feeds only the resolve): before the density march (0), before
-    // the sun visibility (1) or after it (2). Default: after it above 1440p (C3 +0.7 %, C4 +5 % at 3840x2160: the
-    // atmosphere's long transcendental run then overlaps the frame's TAA instead of its SSAO), first otherwise (C2
-    // 1920x1080 -5 % after it); the same bits in every position (profiles/r03_ab_atmos_pos.txt, GPU identity test).
-    const int apos_knob = tuning_knob("SOC_CLOUDS_ATMOS_POS", -1);
-    const int apos = apos_knob >= 0 ? apos_knob : ((long long)W * H > 2560LL * 1440LL ? 2 : 0);
-    // the frame's sky-view table (needs the secondary-ray table; SOC_CLOUDS_SKY_TABLE=0: every pixel evaluated)
-    SkyTab st{};
-    st.t = nullptr;
-    if (lut.t && tuning_knob("SOC_CLOUDS_SKY_TABLE", 1)) {
-        const double r0x = (double)(0.0f + p.cam[0]), r0y = (double)(6372e3f + p.cam[1]), r0z = (double)(0.0f + p.cam[2]);
-        const double rl = std::sqrt(r0x * r0x + r0y * r0y + r0z * r0z);
-        const double ux = r0x / rl, uy = r0y / rl, uz = r0z / rl;
-        const double sx = p.sun[0], sy = p.sun[1], sz = p.sun[2], su = sx * ux + sy * uy + sz * uz;
-        double hx = sx - su * ux, hy = sy - su * uy, hz = sz - su * uz, hl = std::sqrt(hx * hx + hy * hy + hz * hz);
-        if (!(hl > 1e-9)) {   // sun at the zenith: any horizontal axis
-            hx = uy; hy = -ux; hz = 0.0;
-            hl = std::sqrt(hx * hx + hy * hy);
-            if (!(hl > 1e-9)) { hx = 1.0; hy = 0.0; hz = 0.0; hl = 1.0; }
-        }
-        hx /= hl; hy /= hl; hz /= hl;
-        const double bx = uy * hz - uz * hy, by = uz * hx - ux * hz, bz = ux * hy - uy * hx;
-        const double q = (double)kRPlanet / rl;
-        st.t = ws.sky_tab;
-        st.upx = (float)ux; st.upy = (float)uy; st.upz = (float)uz;
-        st.shx = (float)hx; st.shy = (float)hy; st.shz = (float)hz;
-        st.btx = (float)bx; st.bty = (float)by; st.btz = (float)bz;
-        st.eh = q < 1.0 ? (float)std::sqrt(1.0 - q * q) : 0.0f;
-        st.dl = 3e-5f;   // margin inside each branch: the fp32 discriminant is ambiguous within ~1e-5 of the grazing elevation
-        if (!(st.eh > 4.0f * st.dl)) st.t = nullptr;   // camera at or below the surface: no table
-        if (st.t)
-            launch("clouds_sky_table", kWorkgroup, clouds_sky_table, ceil_div(kSvEntries, kWorkgroup), kWorkgroup, 0, s, ws.sky_tab, p,
-                   st, lut);
-    }
-    // with the table the resolve looks the atmosphere up itself (SOC_CLOUDS_ATMOS_FOLD=0: the atmosphere kernel from the table)
-    const bool fold = st.t && tuning_knob("SOC_CLOUDS_ATMOS_FOLD", 1);
-    auto atmos = [&]() {
-        if (fold) return;
-        if (st.t)
-            launch("clouds_atmosphere", kWorkgroup, clouds_atmosphere<true>, grid(res_atmos, blocks), kWorkgroup, 0, s, p, counter,
-                   list, ws.atmos, lut, st);
-        else
-            launch("clouds_atmosphere", kWorkgroup, clouds_atmosphere<false>, grid(res_atmos, blocks), kWorkgroup, 0, s, p, counter,
-                   list, ws.atmos, lut, st);
-    };
-    auto resolve = [&](auto k) {
-        launch("clouds_resolve", kWorkgroup, k, grid_m(res_resolve, blocks), kWorkgroup, 0, s, dimg(noise), dimg(target), p, counter,
-               list, ws.atmos, ws.pb, st);
-    };
-    if (apos == 0) atmos();
-    const DImg nz = dimg(noise);
-    // the resolve's od / vis loads issued in batches of this many steps (1: one step at a time)
-    const int rb = tuning_knob("SOC_CLOUDS_RESOLVE_BATCH", 4);
-    // the density kernel's od scratch read back in batches of this many steps (1: one dense step at a time)
-    const int db = tuning_knob("SOC_CLOUDS_DENSITY_BATCH", 8);
-    // the sun-visibility kernel's next pair word loaded one iteration ahead
-    const bool sv_pf = tuning_knob("SOC_CLOUDS_SUNVIS_PF", 1) != 0;
-    // the sun-visibility kernel's noise table (SOC_CLOUDS_SUNVIS_WIDE): 2 (default) the float-form row table (RowF, 26 KiB
-    // per 512-lane workgroup: 8 waves per SIMD, and room on the CU for the main lane's SSAO tile; C3 1728 -> 1799 fps),
-    // 1 the float-form quads (52 KiB, 6 waves per SIMD), 0 the byte quads (integer form, 26 KiB). The same bits.
-    const int sv_table = tuning_knob("SOC_CLOUDS_SUNVIS_WIDE", 2);
-    const bool sv_wide = sv_table != 0;
-    // one od scratch per workgroup; SOC_CLOUDS_DENSITY_MULT: the grid as this many times the resident set (as gmul).
-    // Default 1: 2 measured C3 1710 -> 1697 fps, C4 1321 -> 1358 (profiles/r05_ab_clouds_density_mult.txt)
-    const int dmul = sky_bound ? 2 : std::max(1, tuning_knob("SOC_CLOUDS_DENSITY_MULT", 1));
-    const int density_grid = std::min((int)std::max(1LL, std::min<long long>((long long)res_density * dmul, blocks)),
-                                      (int)ws.pb.od_blocks);
-    // SOC_CLOUDS_DENSITY_ROWS (default 1): the density kernel's noise from the float-form row table (RowF; the same bits)
-    const bool drows = tuning_knob("SOC_CLOUDS_DENSITY_ROWS", 1) != 0;
-    if (r8) {
-        if (drows) launch("clouds_density", kWorkgroup, clouds_density<true, 8, true>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        else if (db == 4) launch("clouds_density", kWorkgroup, clouds_density<true, 4>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        else if (db == 8) launch("clouds_density", kWorkgroup, clouds_density<true, 8>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        else launch("clouds_density", kWorkgroup, clouds_density<true>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        if (apos == 1) atmos();
-        if (sv_table == 2)
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<true, kSunvisLanes, false, true, true>, grid_m(res_sunvis_r, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        else if (!sv_wide)
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<true, kSunvisLanes, false, true>, grid_m(res_sunvis_n, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        else if (sv_pf)
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<true, kSunvisLanes, true, true>, grid_m(res_sunvis, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        else
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<true, kSunvisLanes, true>, grid_m(res_sunvis, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        if (apos == 2) atmos();
-        if (fold && rb == 4) resolve(clouds_resolve<true, true, 4>);
-        else if (fold && rb == 8) resolve(clouds_resolve<true, true, 8>);
-        else if (fold) resolve(clouds_resolve<true, true>);
-        else resolve(clouds_resolve<true, false>);
-    } else {
-        if (drows) launch("clouds_density", kWorkgroup, clouds_density<false, 8, true>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        else if (db == 4) launch("clouds_density", kWorkgroup, clouds_density<false, 4>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        else if (db == 8) launch("clouds_density", kWorkgroup, clouds_density<false, 8>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        else launch("clouds_density", kWorkgroup, clouds_density<false>, density_grid, kWorkgroup, 0, s, nz, p, counter, list, ws.pb);
-        if (apos == 1) atmos();
-        if (sv_table == 2)
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<false, kSunvisLanes, false, true, true>, grid_m(res_sunvis_r, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        else if (!sv_wide)
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<false, kSunvisLanes, false, true>, grid_m(res_sunvis_n, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        else if (sv_pf)
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<false, kSunvisLanes, true, true>, grid_m(res_sunvis, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        else
-            launch("clouds_sunvis", kSunvisLanes, clouds_sunvis<false, kSunvisLanes, true>, grid_m(res_sunvis, blocks), kSunvisLanes, 0, s, nz, p, list, ws.pb);
-        if (apos == 2) atmos();
-        if (fold && rb == 4) resolve(clouds_resolve<false, true, 4>);
-        else if (fold && rb == 8) resolve(clouds_resolve<false, true, 8>);
-        else if (fold) resolve(clouds_resolve<false, true>);
-        else resolve(clouds_resolve<false, false>);
-    }
-    return check_launch("cloud_rendering");
+}  // namespace soc
+
+extern "C" size_t soc_cloud_rendering_workspace_size(int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return 0;
+    return soc::cloud_ws_layout(nullptr, (size_t)width * (size_t)height).bytes;
 }
-}  // namespace
+
+extern "C" int soc_cloud_rendering(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
+                                   soc_stream stream) {
+    return soc::cloud_rendering_launch(g, depth, noise, target, workspace, stream, false);
+}

@@ -260,7 +260,7 @@ static int abort_frame(soc_renderer* r, hipStream_t s, bool forked, int rc) {
 }
 
 // `out` into the caller's buffer, cut to cap - 1 characters; its whole length.
-static int64_t copy_text(const std::string& out, char* buf, size_t cap) {
+int64_t soc::copy_text(const std::string& out, char* buf, size_t cap) {
     if (buf && cap) {
         const size_t n = std::min(cap - 1, out.size());
         std::memcpy(buf, out.data(), n);

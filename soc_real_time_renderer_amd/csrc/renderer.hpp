@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "cloud_state.hpp"
 #include "soc_internal.hpp"
 
 namespace soc {

@@ -52,10 +52,16 @@ inline hipStream_t hs(soc_stream s) { return reinterpret_cast<hipStream_t>(s); }
 // SOC_CLOUDS_ATMOS_POS, SOC_RENDERER_SSAO_FIRST, SOC_CLOUDS_OD_LUT) and the variants under measurement (SOC_GB_WAVE) are
 // knobs; measured-and-rejected variants are removed.
 int tuning_knob(const char* name, int dflt);
+// Changes with every soc_tuning_reload() (never 0): a launcher on a frame's critical path keeps its block of knobs until
+// this moves, instead of one locked lookup by name per knob and call (the clouds planner, clouds_plan.cpp).
+uint32_t tuning_generation();
 // RN(1 / n) for div_rn (soc_device.hpp), or 0 when n is outside the exhaustively checked range (1..16384).
 inline float recip_rn(int n) {
     return n >= 1 && n <= 16384 ? 1.0f / (float)n : 0.0f;
 }
+
+// `out` into a caller's buffer (truncated to cap - 1 characters and terminated; none when !buf or !cap): its full length.
+int64_t copy_text(const std::string& out, char* buf, size_t cap);
 
 // Checks the launch that was just issued (and a block shape launch() rejected: SOC_E_INVALID_ARG).
 int check_launch(const char* pass);
@@ -105,21 +111,8 @@ bool composition_pair_applicable(const soc_globals* g, const soc_img& target, co
 // soc_cloud_rendering; sky_bound (the render graph's sky lane runs at high priority): the variants that are faster
 // only where the sky lane is the frame's critical path (the density grid at twice the resident set, the classification's
 // hoisted depth samples). The same bits either way.
-// `state` (the render graph's CloudRendering; null: the stateless entry, which builds every table and clears its
-// counter block on every call): the renderer-owned record of what the workspace holds between frames.
-struct CloudState {
-    // static tables (SOC_CLOUDS_STATIC_TABLES, default 1): built when first needed and when their key changes
-    bool od_valid = false, noise_valid = false;
-    uint32_t c2_bits = 0;                 // od table: the bit pattern of dot(pSun, pSun)
-    const void* noise_data = nullptr;     // noise tables: the noise image's (data, format, pitch)
-    int32_t noise_format = 0, noise_pitch = 0;
-    void* workspace = nullptr;            // the workspace the tables and counter blocks were built in
-    // two counter blocks, alternating by frame: frame N uses block N & 1 and its clouds_classify clears the other
-    bool blocks_primed = false;           // both blocks were cleared and every frame since ran the alternating form
-    uint32_t frame = 0;
-    void invalidate_tables() { od_valid = noise_valid = false; }
-    void reset() { *this = CloudState(); }
-};
+// `state`: the renderer-owned record of what the workspace holds between frames (cloud_state.hpp; null: the stateless entry).
+struct CloudState;
 int cloud_rendering_launch(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
                            soc_stream stream, bool sky_bound, CloudState* state = nullptr);
 int sky_compose_launch(const soc_globals* g, soc_img target, soc_img depth, soc_img clouds, uint32_t* scratch,

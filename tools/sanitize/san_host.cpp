@@ -1,6 +1,6 @@
 // san_host — drives the host code under AddressSanitizer + UndefinedBehaviorSanitizer (tools/sanitize/Makefile).
 // No GPU call is made: the globals feed and ECS scene feed, ABI introspection, the render graph (construction,
-// caller passes, derived and ring dependencies, raster head, error paths), the PNG / EXR writers, the scene
+// caller passes, derived and ring dependencies, raster head, error paths), the clouds planner, the PNG / EXR writers, the scene
 // synthesiser, and every pass of the CPU oracle on small images (odd extents included). Exit 0 when every check
 // passes; a sanitizer report aborts the run (-fno-sanitize-recover).
 #include <cmath>
@@ -25,6 +25,10 @@ int soc_scene_terrain_heightmap(int size, uint8_t* rgba);
 // test hook of the frame planner (csrc/render_execute.cpp), not in the public header
 int64_t soc_debug_plan_frame(soc_renderer* r, const soc_globals* g, int32_t phase, int32_t sky_lane_high, int32_t advance,
                              char* buf, size_t cap);
+// test hooks of the clouds planner (csrc/clouds_plan.cpp), not in the public header
+int64_t soc_debug_plan_clouds(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
+                              int32_t sky_bound, const int32_t residency[6], void* state, char* buf, size_t cap);
+size_t soc_debug_cloud_state_bytes(void);
 }
 
 namespace {
@@ -230,6 +234,54 @@ void render_graph(const soc_globals& g, int W, int H) {
     }
 }
 
+// The clouds planner through its test hook (no GPU call; fake, never dereferenced addresses): the single-kernel form, a
+// renderer's frames on one state (primed and built, then cached, then another sun), the per-call form above 1440p, a
+// frame without a sky table, the refusals, a truncated buffer and the length-only call.
+void clouds_plan(const soc_globals& g0, int W, int H) {
+    char* fake = reinterpret_cast<char*>(0x10000000);
+    soc_globals g = g0;
+    const soc_img depth{fake, W, H, W * 4, SOC_FMT_D32F}, target{fake + (1 << 28), W, H, W * 4, SOC_FMT_RGBA8_UNORM};
+    const soc_img noise{fake + (2 << 28), 64, 64, 256, SOC_FMT_RGBA8_UNORM}, r8{fake + (2 << 28), 64, 64, 64, SOC_FMT_R8_UNORM};
+    void* ws = fake + (3 << 28);
+    const int32_t res[6] = {1531, 1543, 769, 773, 787, 1277};
+    std::vector<uint8_t> state(soc_debug_cloud_state_bytes(), 0);
+    char buf[2048];
+    expect(soc_debug_plan_clouds(&g, depth, r8, target, nullptr, 0, res, nullptr, buf, sizeof buf) > 0 &&
+               std::strstr(buf, "kernel\tclouds_kernel\tr8\t") != nullptr, "clouds plan: single kernel");
+    expect(soc_debug_plan_clouds(&g, depth, noise, target, ws, 0, res, state.data(), buf, sizeof buf) > 0 &&
+               std::strstr(buf, "memset\tcounter1\t256\n") != nullptr, "clouds plan: first frame primes the blocks");
+    expect(soc_debug_plan_clouds(&g, depth, noise, target, ws, 1, res, state.data(), buf, sizeof buf) > 0 &&
+               std::strstr(buf, "clouds_od_lut") == nullptr && std::strstr(buf, "\tcounter=1\tzero=0\t") != nullptr,
+           "clouds plan: second frame is cached");
+    g.sun_info.direction[1] *= 0.5f;
+    expect(soc_debug_plan_clouds(&g, depth, noise, target, ws, 0, res, state.data(), buf, sizeof buf) > 0 &&
+               std::strstr(buf, " od=1 noise=0 ") != nullptr, "clouds plan: another sun rebuilds the od table");
+    const soc_img big{fake + (1 << 28), 2562, 1440, 2562 * 4, SOC_FMT_RGBA8_UNORM}, bigd{fake, 2562, 1440, 2562 * 4, SOC_FMT_D32F};
+    g.resolution[0] = 2562;
+    g.resolution[1] = 1440;
+    expect(soc_debug_plan_clouds(&g, bigd, noise, big, ws, 1, res, state.data(), buf, sizeof buf) > 0 &&
+               std::strstr(buf, "\tzero=-1\t") != nullptr, "clouds plan: sky-bound above 1440p builds per call");
+    g.camera_position[1] = -1500.0f;
+    expect(soc_debug_plan_clouds(&g, bigd, noise, big, ws, 0, res, nullptr, buf, sizeof buf) > 0 &&
+               std::strstr(buf, "clouds_sky_table") == nullptr, "clouds plan: no sky table below the surface");
+    expect(soc_debug_plan_clouds(&g, bigd, noise, big, ws, 0, res, nullptr, buf, 16) > 16 && std::strlen(buf) == 15,
+           "clouds plan: truncated");
+    expect(soc_debug_plan_clouds(&g, bigd, noise, big, ws, 0, res, nullptr, nullptr, 0) > 0, "clouds plan: length only");
+    expect(soc_debug_plan_clouds(nullptr, depth, noise, target, ws, 0, res, state.data(), buf, sizeof buf) == SOC_E_INVALID_ARG,
+           "clouds plan: null globals");
+    expect(soc_debug_plan_clouds(&g, target, noise, target, ws, 0, res, nullptr, buf, sizeof buf) == SOC_E_INVALID_ARG,
+           "clouds plan: depth format");
+    expect(soc_debug_plan_clouds(&g, depth, depth, target, ws, 0, res, nullptr, buf, sizeof buf) == SOC_E_UNSUPPORTED,
+           "clouds plan: noise format");
+    const soc_img small{fake + (2 << 28), 64, 32, 256, SOC_FMT_RGBA8_UNORM};
+    expect(soc_debug_plan_clouds(&g, depth, small, target, ws, 0, res, state.data(), buf, sizeof buf) == SOC_E_SHAPE &&
+               std::strstr(buf, "state\tod=0\tnoise=0\t") == buf, "clouds plan: noise extent, the state reset");
+    expect(soc_debug_plan_clouds(&g, depth, noise, target, ws, 0, nullptr, nullptr, buf, sizeof buf) == SOC_E_INVALID_ARG,
+           "clouds plan: null residency");
+    g.resolution[0] = 0;
+    expect(soc_debug_plan_clouds(&g, depth, noise, target, ws, 0, res, nullptr, buf, sizeof buf) == 0, "clouds plan: empty extent");
+}
+
 void writers(int W, int H) {
     HostImg rgba(W, H, SOC_FMT_RGBA8_UNORM, 4, 200);
     HostImg half(W, H, SOC_FMT_RGBA16F, 8);
@@ -374,6 +426,7 @@ int main() {
         globals_and_scene_feed(g, W, H);
         abi_introspection();
         render_graph(g, W, H);
+        clouds_plan(g, W, H);
         writers(W, H);
         oracle_frame(g, W, H);
         oracle_raster(g, W, H);
