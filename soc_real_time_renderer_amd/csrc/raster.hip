@@ -27,11 +27,13 @@
 // sun_shadow_draw_terrain.inl: depth LOAD, LESS_OR_EQUAL) are a layer: the same raster kernels into a visibility buffer of
 // the layer's own (or, depth-only, into the shadow image without the clear), then the resolve's LAYER form, which
 // depth-tests each pixel against the image that is there: see "Terrain layer" below.
-#include <mutex>
-#include <unordered_map>
+// This file holds every raster kernel and the entry points that issue them; the resolve's texture sampler is
+// raster_sampler.hpp, and what the entry points check and lay out before any HIP call is raster_host.cpp.
 #include <vector>
 
 #include "luminance.hpp"
+#include "raster_host.hpp"
+#include "raster_sampler.hpp"
 #include "soc_internal.hpp"
 
 namespace soc {
@@ -57,7 +59,7 @@ struct RasterParams {
     int small_pixels;   // boxes up to this many pixels are scanned by one lane
 };
 
-// workspace: [float4 clip-space screen vertices[V]] [u64 counter, pad..] [uint2 entries[T]]
+// The raster workspace (raster_layout, raster_host.hpp) as pointers.
 // The counter packs (large triangles << 40 | tiles so far): one 64-bit atomicAdd per large triangle
 // returns its entry slot and the first index of its tile range together, so the entries are in
 // increasing range order and a work index finds its triangle by binary search.
@@ -69,19 +71,11 @@ struct Workspace {
 };
 constexpr int ENTRY_SHIFT = 40;
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 inline Workspace carve(void* ws, int V, int T) {
     char* p = static_cast<char*>(ws);
-    Workspace w;
-    w.screen = reinterpret_cast<float4*>(p);
-    size_t off = align_up((size_t)V * 16, 256);
-    w.counter = reinterpret_cast<unsigned long long*>(p + off);
-    off += 256;
-    w.entries = reinterpret_cast<uint2*>(p + off);
-    off = align_up(off + (size_t)T * 8, 256);
-    w.vdata = reinterpret_cast<float4*>(p + off);
-    return w;
+    const RasterLayout l = raster_layout(V, T);
+    return Workspace{reinterpret_cast<float4*>(p), reinterpret_cast<unsigned long long*>(p + l.counter),
+                     reinterpret_cast<uint2*>(p + l.entries), reinterpret_cast<float4*>(p + l.vdata)};
 }
 
 // GLSL mat4 * vec4, summed left to right, no contraction (the oracle's mat_vec).
@@ -407,313 +401,6 @@ struct ResolveParams {
                      // 3 = 8 x 8 / 16 x 16, 4 = 8 x 8 / 8 x 32 (tuning knob SOC_GB_WAVE)
 };
 
-__device__ __forceinline__ float srgb_to_linear(float c) {
-    return c <= 0.04045f ? c / 12.92f : powf((c + 0.055f) / 1.055f, 2.4f);
-}
-
-// lut: srgb_to_linear(unorm8(i)) for i in 0..255 (LDS, filled per workgroup)
-__device__ __forceinline__ f4 decode_rgba8(uint32_t u, bool srgb, const float* lut) {
-    const float a = unorm8(u >> 24);
-    if (!srgb) return f4{unorm8(u & 255u), unorm8((u >> 8) & 255u), unorm8((u >> 16) & 255u), a};
-    return f4{lut[u & 255u], lut[(u >> 8) & 255u], lut[(u >> 16) & 255u], a};
-}
-__device__ __forceinline__ f4 texel_rgba8(const DImg& im, int x, int y, bool srgb, const float* lut) {
-    return decode_rgba8(row_ptr<uint32_t>(im, y)[x], srgb, lut);
-}
-
-typedef uint32_t u2a4 __attribute__((ext_vector_type(2))) __attribute__((aligned(4)));
-// The two texels (x0, y), (x1, y) of a bilinear tap's row: one 8-byte load when x1 = x0 + 1 (every tap that does
-// not wrap around the REPEAT edge), else two. The same texels either way.
-__device__ __forceinline__ void texel_row_pair(const DImg& im, int x0, int x1, int y, uint32_t& a, uint32_t& b) {
-    const uint32_t* row = row_ptr<uint32_t>(im, y);
-    if (x1 == x0 + 1) {
-        const u2a4 t = *reinterpret_cast<const u2a4*>(row + x0);
-        a = t.x;
-        b = t.y;
-    } else {
-        a = row[x0];
-        b = row[x1];
-    }
-}
-
-// REPEAT axis of extent n: the power-of-two mask when n is one (every texture of the reference's assets),
-// else the general modulo; same taps and weight either way.
-__device__ __forceinline__ Axis axis_repeat_level(float u, int n) {
-    return (n & (n - 1)) ? axis_repeat_any(u, n) : axis_repeat_pow2(u, n, n - 1);
-}
-
-// Bilinear REPEAT sample of one level (its image view already resolved) of a packed mip chain, from the
-// level's two axes (computed once when two textures of the same extent share them).
-#ifndef SOC_GB_FAST_FILTER
-#define SOC_GB_FAST_FILTER 1
-#endif
-#if SOC_GB_FAST_FILTER
-typedef unsigned short gb_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t gb_udot2(uint32_t a, uint32_t b) {
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(gb_u16x2, a), __builtin_bit_cast(gb_u16x2, b), 0u, false);
-}
-// Bilinear of the RGBA8 texels a b (top row) / c d with the contract's 8-bit weights (w = k / 256, exact).
-// UNORM: the exact integer bilinear per channel (v_dot2_u32_u16: a_k (256 - kx) + b_k kx per row, then across the rows;
-// at most 255 * 65536 < 2^24, exact in fp32), one conversion and one scale per channel. sRGB: the LUT-decoded channels,
-// each lerp fma(w, q - p, p). Against the oracle's unorm8-then-lerp chain this changes fp32 roundings only (the
-// G-buffer's RGBA16F tolerance; the GPU LUT already differs from the oracle's powf by an ulp).
-__device__ __forceinline__ f4 bilerp_rgba8(uint32_t ua, uint32_t ub, uint32_t uc, uint32_t ud, float wx, float wy, bool srgb,
-                                           const float* lut) {
-    if (!srgb) {
-        const uint32_t kx = (uint32_t)(wx * 256.0f), ky = (uint32_t)(wy * 256.0f);
-        const uint32_t wxp = (256u - kx) | (kx << 16), wyp = (256u - ky) | (ky << 16);
-        constexpr float kScale = 1.0f / (255.0f * 65536.0f);
-        auto ch = [&](uint32_t k) {   // channel k: bytes k of (a, b) and of (c, d) as 16-bit pairs
-            const uint32_t sel = k | 0x0c00u | ((4u + k) << 16) | 0x0c000000u;
-            const uint32_t top = gb_udot2(__builtin_amdgcn_perm(ub, ua, sel), wxp);
-            const uint32_t bot = gb_udot2(__builtin_amdgcn_perm(ud, uc, sel), wxp);
-            return (float)gb_udot2(top | (bot << 16), wyp) * kScale;
-        };
-        return f4{ch(0), ch(1), ch(2), ch(3)};
-    }
-    auto ch = [&](float a, float b, float c, float d) {
-        const float top = __builtin_fmaf(wx, b - a, a), bot = __builtin_fmaf(wx, d - c, c);
-        return __builtin_fmaf(wy, bot - top, top);
-    };
-    return f4{ch(lut[ua & 255u], lut[ub & 255u], lut[uc & 255u], lut[ud & 255u]),
-              ch(lut[(ua >> 8) & 255u], lut[(ub >> 8) & 255u], lut[(uc >> 8) & 255u], lut[(ud >> 8) & 255u]),
-              ch(lut[(ua >> 16) & 255u], lut[(ub >> 16) & 255u], lut[(uc >> 16) & 255u], lut[(ud >> 16) & 255u]),
-              ch(unorm8(ua >> 24), unorm8(ub >> 24), unorm8(uc >> 24), unorm8(ud >> 24))};
-}
-// trilinear blend of two levels' samples: fma(f, s1 - s0, s0) per channel
-__device__ __forceinline__ f4 lerp_levels(f4 s0, f4 s1, float f) {
-    return f4{__builtin_fmaf(f, s1.x - s0.x, s0.x), __builtin_fmaf(f, s1.y - s0.y, s0.y), __builtin_fmaf(f, s1.z - s0.z, s0.z),
-              __builtin_fmaf(f, s1.w - s0.w, s0.w)};
-}
-#else
-__device__ __forceinline__ f4 lerp_levels(f4 s0, f4 s1, float f) {
-    return f4{lerp_w(s0.x, s1.x, f), lerp_w(s0.y, s1.y, f), lerp_w(s0.z, s1.z, f), lerp_w(s0.w, s1.w, f)};
-}
-#endif
-
-__device__ __forceinline__ f4 sample_level_ax(const DImg& im, const Axis& ax, const Axis& ay, bool srgb, const float* lut) {
-    uint32_t ua, ub, uc, ud;
-    texel_row_pair(im, ax.i0, ax.i1, ay.i0, ua, ub);
-    texel_row_pair(im, ax.i0, ax.i1, ay.i1, uc, ud);
-#if SOC_GB_FAST_FILTER
-    return bilerp_rgba8(ua, ub, uc, ud, ax.w, ay.w, srgb, lut);
-#else
-    const f4 a = decode_rgba8(ua, srgb, lut), b = decode_rgba8(ub, srgb, lut);
-    const f4 c = decode_rgba8(uc, srgb, lut), d = decode_rgba8(ud, srgb, lut);
-    return bilerp4(a, b, c, d, ax.w, ay.w);
-#endif
-}
-__device__ __forceinline__ f4 sample_texture(const soc_img& tex, float u, float v, const float* lut) {
-    if (!tex.data) return f4{1.0f, 1.0f, 1.0f, 1.0f};
-    const DImg im{static_cast<char*>(tex.data), tex.width, tex.height, tex.pitch_bytes};
-    const bool srgb = tex.format == SOC_FMT_RGBA8_SRGB;
-    return sample_level_ax(im, axis_repeat_level(u, tex.width), axis_repeat_level(v, tex.height), srgb, lut);
-}
-
-
-__device__ __forceinline__ f4 sample_level(const DImg& im, float u, float v, bool srgb, const float* lut) {
-    return sample_level_ax(im, axis_repeat_level(u, im.w), axis_repeat_level(v, im.h), srgb, lut);
-}
-__device__ __forceinline__ DImg level_view(const soc_img& tex, int k) {
-    int wk, hk;
-    const size_t off = mip_offset(tex.width, tex.height, tex.pitch_bytes, k, wk, hk);
-    return DImg{static_cast<char*>(tex.data) + off, wk, hk, k ? 4 * wk : tex.pitch_bytes};
-}
-
-// Fine uv derivatives of the pixel's quad.
-struct UVGrad { float dudx, dvdx, dudy, dvdy; };
-
-// Trilinear + anisotropic REPEAT sample of a mip-chained texture (soc_rt.h SOC_MATERIAL_MIPMAPPED).
-__device__ __forceinline__ f4 sample_texture_mip(const soc_img& tex, float u, float v, const UVGrad& gr, float max_aniso, const float* lut) {
-#pragma clang fp contract(off)
-    if (!tex.data) return f4{1.0f, 1.0f, 1.0f, 1.0f};
-    const bool srgb = tex.format == SOC_FMT_RGBA8_SRGB;
-    const int L = mip_levels(tex.width, tex.height);
-    const float W = (float)tex.width, H = (float)tex.height;
-    const float ax = gr.dudx * W, ay = gr.dvdx * H, bx = gr.dudy * W, by = gr.dvdy * H;
-    const float px = sqrtf(ax * ax + ay * ay), py = sqrtf(bx * bx + by * by);
-    const float pmax = fmaxf(px, py), pmin = fminf(px, py);
-    int n = 1;
-    if (max_aniso > 1.0f && pmax > 0.0f && pmax <= 3.4e38f) {
-        const float cap = floorf(max_aniso);
-        n = (int)(pmin > 0.0f ? fminf(ceilf(pmax / pmin), cap) : cap);
-    }
-    int lq = 0;   // lod in 1/256 steps, clamped to [0, (L - 1) 256]
-    const float rho = pmax / (float)n;
-    if (rho > 0.0f && rho <= 3.4e38f) {
-        const float lam = fminf(fmaxf(det_log2(rho), -64.0f), 64.0f);
-        lq = min(max((int)floorf(lam * 256.0f + 0.5f), 0), (L - 1) * 256);
-    }
-    const int l0 = lq >> 8;
-    const float f = (float)(lq & 255) * (1.0f / 256.0f);
-    const DImg im0 = level_view(tex, l0), im1 = level_view(tex, min(l0 + 1, L - 1));
-    const bool xmajor = px >= py;
-    const float du = xmajor ? gr.dudx : gr.dudy, dv = xmajor ? gr.dvdx : gr.dvdy;
-    f4 acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int i = 1; i <= n; ++i) {
-        float su = u, sv = v;
-        if (n > 1) {
-            const float t = (float)i / (float)(n + 1) - 0.5f;
-            su = u + t * du;
-            sv = v + t * dv;
-        }
-        f4 s0 = sample_level(im0, su, sv, srgb, lut);
-        if (lq & 255) s0 = lerp_levels(s0, sample_level(im1, su, sv, srgb, lut), f);
-        acc = f4{acc.x + s0.x, acc.y + s0.y, acc.z + s0.z, acc.w + s0.w};
-    }
-    if (n == 1) return acc;
-    const float fn = (float)n;
-    return f4{acc.x / fn, acc.y / fn, acc.z / fn, acc.w / fn};
-}
-
-// sample_texture_mip of two textures of the same extent at the same uv (the material's normal image and
-// albedo): the footprint, tap count, lod and every tap's level axes depend only on the extent, so they are
-// computed once; each texture's taps, lerps and sums are sample_texture_mip's, in its order (same bits).
-// Precondition: both have data and ta.width == tb.width, ta.height == tb.height.
-__device__ __forceinline__ void sample_texture_mip2(const soc_img& ta, const soc_img& tb, float u, float v, const UVGrad& gr,
-                                    float max_aniso, const float* lut, f4& ra, f4& rb) {
-#pragma clang fp contract(off)
-    const bool sa = ta.format == SOC_FMT_RGBA8_SRGB, sb = tb.format == SOC_FMT_RGBA8_SRGB;
-    const int L = mip_levels(ta.width, ta.height);
-    const float W = (float)ta.width, H = (float)ta.height;
-    const float ax = gr.dudx * W, ay = gr.dvdx * H, bx = gr.dudy * W, by = gr.dvdy * H;
-    const float px = sqrtf(ax * ax + ay * ay), py = sqrtf(bx * bx + by * by);
-    const float pmax = fmaxf(px, py), pmin = fminf(px, py);
-    int n = 1;
-    if (max_aniso > 1.0f && pmax > 0.0f && pmax <= 3.4e38f) {
-        const float cap = floorf(max_aniso);
-        n = (int)(pmin > 0.0f ? fminf(ceilf(pmax / pmin), cap) : cap);
-    }
-    int lq = 0;
-    const float rho = pmax / (float)n;
-    if (rho > 0.0f && rho <= 3.4e38f) {
-        const float lam = fminf(fmaxf(det_log2(rho), -64.0f), 64.0f);
-        lq = min(max((int)floorf(lam * 256.0f + 0.5f), 0), (L - 1) * 256);
-    }
-    const int l0 = lq >> 8, l1 = min(l0 + 1, L - 1);
-    const float f = (float)(lq & 255) * (1.0f / 256.0f);
-    const DImg a0 = level_view(ta, l0), a1 = level_view(ta, l1), b0 = level_view(tb, l0), b1 = level_view(tb, l1);
-    const bool xmajor = px >= py;
-    const float du = xmajor ? gr.dudx : gr.dudy, dv = xmajor ? gr.dvdx : gr.dvdy;
-    f4 acca = f4{0.0f, 0.0f, 0.0f, 0.0f}, accb = acca;
-    auto tri = [&](f4 s0, const f4& s1) { return lerp_levels(s0, s1, f); };
-    for (int i = 1; i <= n; ++i) {
-        float su = u, sv = v;
-        if (n > 1) {
-            const float t = (float)i / (float)(n + 1) - 0.5f;
-            su = u + t * du;
-            sv = v + t * dv;
-        }
-        const Axis x0 = axis_repeat_level(su, a0.w), y0 = axis_repeat_level(sv, a0.h);
-        f4 pa = sample_level_ax(a0, x0, y0, sa, lut), pb = sample_level_ax(b0, x0, y0, sb, lut);
-        if (lq & 255) {
-            const Axis x1 = axis_repeat_level(su, a1.w), y1 = axis_repeat_level(sv, a1.h);
-            pa = tri(pa, sample_level_ax(a1, x1, y1, sa, lut));
-            pb = tri(pb, sample_level_ax(b1, x1, y1, sb, lut));
-        }
-        acca = f4{acca.x + pa.x, acca.y + pa.y, acca.z + pa.z, acca.w + pa.w};
-        accb = f4{accb.x + pb.x, accb.y + pb.y, accb.z + pb.z, accb.w + pb.w};
-    }
-    if (n == 1) {
-        ra = acca;
-        rb = accb;
-        return;
-    }
-    const float fn = (float)n;
-    ra = f4{acca.x / fn, acca.y / fn, acca.z / fn, acca.w / fn};
-    rb = f4{accb.x / fn, accb.y / fn, accb.z / fn, accb.w / fn};
-}
-
-// sample_texture_mip2 from the material's paired texels (soc_pair_textures: albedo and normal texel interleaved, 8 B):
-// each tap row of both textures is one 16-B load (two 8-B loads at the REPEAT seam) instead of one 8-B load per
-// texture. The same texels reach the same filter arithmetic: the same bits as sample_texture_mip2 (GPU test).
-__device__ __forceinline__ DImg paired_level(const void* paired, int W, int H, int k) {
-    int wk, hk;
-    const size_t off = mip_offset(W, H, 8 * W, k, wk, hk, 8);
-    return DImg{static_cast<char*>(const_cast<void*>(paired)) + off, wk, hk, 8 * wk};
-}
-typedef uint32_t u4a8g __attribute__((ext_vector_type(4))) __attribute__((aligned(8)));
-__device__ __forceinline__ void paired_row(const DImg& im, int x0, int x1, int y, uint32_t& a0, uint32_t& n0, uint32_t& a1,
-                                           uint32_t& n1) {
-    const uint2* row = row_ptr<uint2>(im, y);
-    if (x1 == x0 + 1) {
-        const u4a8g t = *reinterpret_cast<const u4a8g*>(row + x0);
-        a0 = t.x; n0 = t.y; a1 = t.z; n1 = t.w;
-    } else {
-        const uint2 p = row[x0], q = row[x1];
-        a0 = p.x; n0 = p.y; a1 = q.x; n1 = q.y;
-    }
-}
-__device__ __forceinline__ void sample_paired_level(const DImg& im, const Axis& ax, const Axis& ay, bool sn, bool sa,
-                                                    const float* lut, f4& rn, f4& ra) {
-    uint32_t a0, n0, a1, n1, a2, n2, a3, n3;
-    paired_row(im, ax.i0, ax.i1, ay.i0, a0, n0, a1, n1);
-    paired_row(im, ax.i0, ax.i1, ay.i1, a2, n2, a3, n3);
-#if SOC_GB_FAST_FILTER
-    rn = bilerp_rgba8(n0, n1, n2, n3, ax.w, ay.w, sn, lut);
-    ra = bilerp_rgba8(a0, a1, a2, a3, ax.w, ay.w, sa, lut);
-#else
-    rn = bilerp4(decode_rgba8(n0, sn, lut), decode_rgba8(n1, sn, lut), decode_rgba8(n2, sn, lut), decode_rgba8(n3, sn, lut), ax.w, ay.w);
-    ra = bilerp4(decode_rgba8(a0, sa, lut), decode_rgba8(a1, sa, lut), decode_rgba8(a2, sa, lut), decode_rgba8(a3, sa, lut), ax.w, ay.w);
-#endif
-}
-// ta: the normal image, tb: the albedo (their extent and formats); results as sample_texture_mip2's (ra: normal, rb: albedo)
-__device__ __forceinline__ void sample_texture_mip2p(const soc_img& ta, const soc_img& tb, const void* paired, float u, float v,
-                                                     const UVGrad& gr, float max_aniso, const float* lut, f4& ra, f4& rb) {
-#pragma clang fp contract(off)
-    const bool sa = ta.format == SOC_FMT_RGBA8_SRGB, sb = tb.format == SOC_FMT_RGBA8_SRGB;
-    const int L = mip_levels(ta.width, ta.height);
-    const float W = (float)ta.width, H = (float)ta.height;
-    const float ax = gr.dudx * W, ay = gr.dvdx * H, bx = gr.dudy * W, by = gr.dvdy * H;
-    const float px = sqrtf(ax * ax + ay * ay), py = sqrtf(bx * bx + by * by);
-    const float pmax = fmaxf(px, py), pmin = fminf(px, py);
-    int n = 1;
-    if (max_aniso > 1.0f && pmax > 0.0f && pmax <= 3.4e38f) {
-        const float cap = floorf(max_aniso);
-        n = (int)(pmin > 0.0f ? fminf(ceilf(pmax / pmin), cap) : cap);
-    }
-    int lq = 0;
-    const float rho = pmax / (float)n;
-    if (rho > 0.0f && rho <= 3.4e38f) {
-        const float lam = fminf(fmaxf(det_log2(rho), -64.0f), 64.0f);
-        lq = min(max((int)floorf(lam * 256.0f + 0.5f), 0), (L - 1) * 256);
-    }
-    const int l0 = lq >> 8, l1 = min(l0 + 1, L - 1);
-    const float f = (float)(lq & 255) * (1.0f / 256.0f);
-    const DImg p0 = paired_level(paired, ta.width, ta.height, l0), p1 = paired_level(paired, ta.width, ta.height, l1);
-    const bool xmajor = px >= py;
-    const float du = xmajor ? gr.dudx : gr.dudy, dv = xmajor ? gr.dvdx : gr.dvdy;
-    f4 acca = f4{0.0f, 0.0f, 0.0f, 0.0f}, accb = acca;
-    for (int i = 1; i <= n; ++i) {
-        float su = u, sv = v;
-        if (n > 1) {
-            const float t = (float)i / (float)(n + 1) - 0.5f;
-            su = u + t * du;
-            sv = v + t * dv;
-        }
-        const Axis x0 = axis_repeat_level(su, p0.w), y0 = axis_repeat_level(sv, p0.h);
-        f4 pa, pb;
-        sample_paired_level(p0, x0, y0, sa, sb, lut, pa, pb);
-        if (lq & 255) {
-            const Axis x1 = axis_repeat_level(su, p1.w), y1 = axis_repeat_level(sv, p1.h);
-            f4 qa, qb;
-            sample_paired_level(p1, x1, y1, sa, sb, lut, qa, qb);
-            pa = lerp_levels(pa, qa, f);
-            pb = lerp_levels(pb, qb, f);
-        }
-        acca = f4{acca.x + pa.x, acca.y + pa.y, acca.z + pa.z, acca.w + pa.w};
-        accb = f4{accb.x + pb.x, accb.y + pb.y, accb.z + pb.z, accb.w + pb.w};
-    }
-    if (n == 1) {
-        ra = acca;
-        rb = accb;
-        return;
-    }
-    const float fn = (float)n;
-    ra = f4{acca.x / fn, acca.y / fn, acca.z / fn, acca.w / fn};
-    rb = f4{accb.x / fn, accb.y / fn, accb.z / fn, accb.w / fn};
-}
-
 __device__ __forceinline__ f3 mat3_vec_exact(const Mat3& M, f3 v) {
 #pragma clang fp contract(off)
     const float* m = M.m;
@@ -747,6 +434,17 @@ __device__ __forceinline__ f3 normalize_exact(f3 a) {
 // 4 float4 per vertex; computed once per vertex into the workspace (gbuffer_vertex_setup) or inline by
 // the resolve; the same function either way, so both give the same bits.
 struct VtxData { float4 s, n, cc, pc; };
+// d by value: by reference, the two draws kernels (which call this from a lambda) came out with another schedule
+__device__ __forceinline__ void store_vertex(float4* vd, int i, VtxData d) {
+    vd[4 * i] = d.s;
+    vd[4 * i + 1] = d.n;
+    vd[4 * i + 2] = d.cc;
+    vd[4 * i + 3] = d.pc;
+}
+// f32mat3x3(normal_matrix): the upper 3x3 of a column-major 4x4
+__host__ __device__ __forceinline__ Mat3 normal3_of(const float m[16]) {
+    return Mat3{{m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]}};
+}
 
 __device__ __forceinline__ VtxData vertex_data(const soc_mesh& mesh, uint32_t v, const ResolveParams& p) {
 #pragma clang fp contract(off)
@@ -783,11 +481,7 @@ __device__ __forceinline__ VtxData vertex_data_motion(const soc_mesh& mesh, uint
 __global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup(soc_mesh mesh, float4* __restrict__ vd, ResolveParams p) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= mesh.vertex_count) return;
-    const VtxData d = vertex_data(mesh, (uint32_t)v, p);
-    vd[4 * v] = d.s;
-    vd[4 * v + 1] = d.n;
-    vd[4 * v + 2] = d.cc;
-    vd[4 * v + 3] = d.pc;
+    store_vertex(vd, v, vertex_data(mesh, (uint32_t)v, p));
 }
 
 template <bool PRE>
@@ -964,40 +658,6 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(SOC_
     row_ptr_w<uint2>(normal, y)[x] = pack_h4(f4{n.x, n.y, n.z, 1.0f});
 }
 
-int check_mesh(const soc_mesh* mesh, const char* pass, bool attributes) {
-    if (!mesh || !mesh->positions || !mesh->indices || mesh->vertex_count < 0 || mesh->triangle_count < 0)
-        return set_error(SOC_E_INVALID_ARG, "%s: null mesh / positions / indices or negative counts", pass);
-    if (attributes && (!mesh->normals || !mesh->uvs))
-        return set_error(SOC_E_INVALID_ARG, "%s: the G-buffer resolve needs normals and uvs", pass);
-    if ((uint32_t)mesh->triangle_count >= 0xFFFFFFFEu)
-        return set_error(SOC_E_SHAPE, "%s: too many triangles for the visibility key", pass);
-    return SOC_OK;
-}
-
-RasterParams make_raster_params(const soc_mesh* mesh, const float* vp, int W, int H, int cull) {
-    RasterParams p{};
-    p.model = mat4(mesh->model_matrix);
-    p.vp = mat4(vp);
-    p.width = W;
-    p.height = H;
-    p.vertex_count = mesh->vertex_count;
-    p.triangle_count = mesh->triangle_count;
-    p.cull = cull;
-    p.small_pixels = SMALL_PIXELS;
-    return p;
-}
-
-int launch_raster(const soc_mesh* mesh, const RasterParams& p, void* target, size_t pitch, void* workspace,
-                  hipStream_t s, const char* pass) {
-    Workspace ws = carve(workspace, mesh->vertex_count, mesh->triangle_count);
-    launch("raster_setup", kWorkgroup, raster_setup, ceil_div(max(mesh->vertex_count, 1), 256), kWorkgroup, 0, s, mesh->positions, ws, p);
-    if (mesh->triangle_count > 0) {
-        launch("raster_small", kWorkgroup, raster_small, ceil_div(mesh->triangle_count, 256), kWorkgroup, 0, s, mesh->indices, ws, p, target, pitch);
-        launch("raster_big", kWorkgroup, raster_big, 2048, kWorkgroup, 0, s, mesh->indices, ws, p, target, pitch);
-    }
-    return check_launch(pass);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Draw scenes (soc_rt.h "Draw scenes"): per-entity draws with their own transforms
 // ------------------------------------------------------------------------------------------------
@@ -1015,67 +675,23 @@ int launch_raster(const soc_mesh* mesh, const RasterParams& p, void* target, siz
 // raster_small, raster_big and gbuffer_resolve<true> then run UNCHANGED on a single-mesh view of the tables (slot count
 // as the vertex count, the rebased indices, the slot uvs, the per-triangle materials): a triangle's global id is its
 // position in the rebased index buffer, so the keys and the tie rule are the serial draw loop's.
-struct DrawRec {   // device copy of a draw with its prefix sums
-    int32_t first_index, triangle_count, vertex_offset, first_vertex, vertex_count, transform, material;
-    int32_t slot_base, triangle_base;
-};
 
-// workspace: [u32 first failing draw (0xFFFFFFFF: none), pad to 256] [uint2 slots[S]] [float2 slot uvs[S]]
-//            [u32 rebased indices[3 T]] [u32 triangle materials[T]] [DrawRec[D]] [raster workspace of (S, T)] x 2 views
-struct DrawWorkspace {
-    uint32_t* flag;
+struct DrawWorkspace {    // the draw-scene workspace (draw_layout, raster_host.hpp) as pointers
+    uint32_t* flag;       // first failing draw (DRAWS_OK: none)
     uint2* slots;         // {source vertex, transform}
     float2* slot_uvs;
-    uint32_t* indices;
-    uint32_t* materials;
+    uint32_t *indices, *materials;
     DrawRec* draws;
     void* view[2];        // 0: the camera (visibility, G-buffer vertex data), 1: the sun (depth)
 };
-constexpr uint32_t DRAWS_OK = 0xFFFFFFFFu;
-
-struct DrawTotals { long long slots = 0, triangles = 0; };
-
-// Slot and triangle totals of a draw list; false on a null list, a negative count or field, or totals beyond int32.
-bool draw_totals(const soc_draw* draws, int32_t draw_count, DrawTotals& t) {
-    if (draw_count < 0 || (draw_count > 0 && !draws)) return false;
-    for (int32_t d = 0; d < draw_count; ++d) {
-        if (draws[d].triangle_count < 0 || draws[d].vertex_count < 0 || draws[d].first_vertex < 0 || draws[d].first_index < 0)
-            return false;
-        t.slots += draws[d].vertex_count;
-        t.triangles += draws[d].triangle_count;
-    }
-    return t.slots <= 0x7FFFFFFFll && t.triangles <= 0x7FFFFFFFll;
-}
-
-size_t draw_tables_bytes(long long S, long long T, int32_t D) {
-    size_t off = 256;
-    off = align_up(off + (size_t)S * 8, 256);
-    off = align_up(off + (size_t)S * 8, 256);
-    off = align_up(off + (size_t)T * 12, 256);
-    off = align_up(off + (size_t)T * 4, 256);
-    off = align_up(off + (size_t)D * sizeof(DrawRec), 256);
-    return off;
-}
 
 DrawWorkspace draw_carve(void* ws, long long S, long long T, int32_t D) {
     char* p = static_cast<char*>(ws);
-    DrawWorkspace w;
-    w.flag = reinterpret_cast<uint32_t*>(p);
-    size_t off = 256;
-    w.slots = reinterpret_cast<uint2*>(p + off);
-    off = align_up(off + (size_t)S * 8, 256);
-    w.slot_uvs = reinterpret_cast<float2*>(p + off);
-    off = align_up(off + (size_t)S * 8, 256);
-    w.indices = reinterpret_cast<uint32_t*>(p + off);
-    off = align_up(off + (size_t)T * 12, 256);
-    w.materials = reinterpret_cast<uint32_t*>(p + off);
-    off = align_up(off + (size_t)T * 4, 256);
-    w.draws = reinterpret_cast<DrawRec*>(p + off);
-    off = align_up(off + (size_t)D * sizeof(DrawRec), 256);
-    const size_t view = align_up(soc_raster_workspace_size((int32_t)S, (int32_t)T), 256);
-    w.view[0] = p + off;
-    w.view[1] = p + off + view;
-    return w;
+    const DrawLayout l = draw_layout(S, T, D);
+    return DrawWorkspace{reinterpret_cast<uint32_t*>(p), reinterpret_cast<uint2*>(p + l.slots),
+                         reinterpret_cast<float2*>(p + l.slot_uvs), reinterpret_cast<uint32_t*>(p + l.indices),
+                         reinterpret_cast<uint32_t*>(p + l.materials), reinterpret_cast<DrawRec*>(p + l.draws),
+                         {p + l.view[0], p + l.view[1]}};
 }
 
 // The last draw whose base (slot_base or triangle_base) is <= i. Empty draws share their base with the next draw, so
@@ -1189,14 +805,9 @@ __global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup_draws(soc_mes
     with_slot_transform(xf, sl.y, [&](const soc_transform& t) {
         ResolveParams q = p;
         q.model = mat4_of(t.model_matrix);
-        const float* nm = t.normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
-        q.normal3 = Mat3{{nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]}};
+        q.normal3 = normal3_of(t.normal_matrix);
         const VtxData d = vertex_data(mesh, sl.x, q);
-        if (!live) return;
-        vd[4 * i] = d.s;
-        vd[4 * i + 1] = d.n;
-        vd[4 * i + 2] = d.cc;
-        vd[4 * i + 3] = d.pc;
+        if (live) store_vertex(vd, i, d);
     });
 }
 
@@ -1243,177 +854,80 @@ __global__ __launch_bounds__(kWorkgroup) void gbuffer_vertex_setup_draws_motion(
     with_slot_transform_motion(xf, prev, sl.y, [&](const soc_transform& t, const float* prev_model) {
         ResolveParams q = p;
         q.model = mat4_of(t.model_matrix);
-        const float* nm = t.normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
-        q.normal3 = Mat3{{nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]}};
+        q.normal3 = normal3_of(t.normal_matrix);
         const VtxData d = vertex_data_motion(mesh, sl.x, q, mat4_of(prev_model));
-        if (!live) return;
-        vd[4 * i] = d.s;
-        vd[4 * i + 1] = d.n;
-        vd[4 * i + 2] = d.cc;
-        vd[4 * i + 3] = d.pc;
+        if (live) store_vertex(vd, i, d);
     });
 }
 
-// What the library remembers of a built workspace: a fingerprint of everything the static tables were built from, the
-// totals, and the first draw the device validation rejected (DRAWS_OK: none).
-struct DrawBuilt {
-    uint64_t fingerprint;
-    uint32_t failed_draw;
+// ------------------------------------------------------------------------------------------------
+// Issuing: the clears, one raster ladder, one resolve
+// ------------------------------------------------------------------------------------------------
+void clear_visibility(uint64_t* visibility, int W, int H, hipStream_t s) {
+    const size_t n = (size_t)W * H;
+    launch("raster_clear_vis", kWorkgroup, raster_clear_vis, (unsigned)((n + 255) / 256), kWorkgroup, 0, s,
+           reinterpret_cast<unsigned long long*>(visibility), n);
+}
+// depth clear 1.0 (sun_shadow_draw.inl:71-74): the width texels of each row only, a padded view's bytes between the rows
+// belong to the caller
+void clear_depth(const soc_img& depth, hipStream_t s) {
+    launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)),
+           kWorkgroup, 0, s, static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
+}
+
+// Where a raster call's triangles come from, with the raster workspace of (V, T) to use: a mesh (raster_setup with its
+// model matrix) or a built draw scene's tables (slots: raster_setup_draws per slot, each with its transform's model matrix;
+// p.model stays zero).
+struct RasterSource {
+    const float *positions, *model;
+    const uint32_t* indices;
+    int V, T;
+    void* workspace;
+    const uint2* slots;
+    const soc_transform* transforms;
 };
-std::mutex g_draws_mutex;
-std::unordered_map<const void*, DrawBuilt> g_draws_built;
-
-uint64_t fnv1a(uint64_t h, const void* data, size_t n) {
-    const unsigned char* b = static_cast<const unsigned char*>(data);
-    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-    return h;
+RasterSource mesh_source(const soc_mesh* m, void* workspace) {
+    return RasterSource{m->positions, m->model_matrix, m->indices, m->vertex_count, m->triangle_count, workspace, nullptr, nullptr};
 }
-uint64_t draw_fingerprint(const soc_draw_scene* sc) {
-    uint64_t h = 14695981039346656037ull;
-    h = fnv1a(h, &sc->indices, sizeof sc->indices);
-    h = fnv1a(h, &sc->uvs, sizeof sc->uvs);
-    h = fnv1a(h, &sc->vertex_count, sizeof sc->vertex_count);
-    h = fnv1a(h, &sc->index_count, sizeof sc->index_count);
-    h = fnv1a(h, &sc->draw_count, sizeof sc->draw_count);
-    if (sc->draw_count > 0) h = fnv1a(h, sc->draws, (size_t)sc->draw_count * sizeof(soc_draw));
-    return h;
-}
-
-// Everything the host can check of a draw scene, before any HIP call.
-int check_draw_scene(const soc_draw_scene* sc, const char* pass, bool attributes, DrawTotals& tot) {
-    if (!sc) return set_error(SOC_E_INVALID_ARG, "%s: null scene", pass);
-    if (!sc->positions || !sc->indices || !sc->transforms || !sc->workspace || sc->vertex_count < 0 || sc->index_count < 0 ||
-        sc->draw_count < 0 || (sc->draw_count > 0 && !sc->draws) || sc->transform_count <= 0 || sc->material_count <= 0)
-        return set_error(SOC_E_INVALID_ARG, "%s: null positions / indices / draws / transforms / workspace or bad counts", pass);
-    if (attributes && (!sc->normals || !sc->uvs))
-        return set_error(SOC_E_INVALID_ARG, "%s: the G-buffer resolve needs normals and uvs", pass);
-    if (reinterpret_cast<uintptr_t>(sc->workspace) % 256)
-        return set_error(SOC_E_INVALID_ARG, "%s: the workspace must be 256-byte aligned", pass);
-    long long triangles = 0;
-    for (int32_t i = 0; i < sc->draw_count; ++i) {
-        const soc_draw& d = sc->draws[i];
-        if (d.triangle_count < 0 || d.vertex_count < 0 || d.first_vertex < 0 || d.first_index < 0)
-            return set_error(SOC_E_INVALID_ARG, "%s: draw %d: negative first_index, triangle_count or vertex range", pass, i);
-        if ((long long)d.first_index + 3ll * d.triangle_count > sc->index_count)
-            return set_error(SOC_E_SHAPE, "%s: draw %d: first_index %d + 3 x %d triangles exceed index_count %d", pass, i,
-                             d.first_index, d.triangle_count, sc->index_count);
-        if ((long long)d.first_vertex + d.vertex_count > sc->vertex_count)
-            return set_error(SOC_E_SHAPE, "%s: draw %d: vertex range [%d, %d + %d) exceeds vertex_count %d", pass, i,
-                             d.first_vertex, d.first_vertex, d.vertex_count, sc->vertex_count);
-        if (d.transform < 0 || d.transform >= sc->transform_count)
-            return set_error(SOC_E_SHAPE, "%s: draw %d: transform %d outside the %d transforms", pass, i, d.transform,
-                             sc->transform_count);
-        if (d.material < 0 || d.material >= sc->material_count)
-            return set_error(SOC_E_SHAPE, "%s: draw %d: material %d outside the %d materials", pass, i, d.material,
-                             sc->material_count);
-        triangles += d.triangle_count;
-        if (triangles >= 0xFFFFFFFEll)
-            return set_error(SOC_E_SHAPE, "%s: too many triangles for the visibility key", pass);
-    }
-    tot = DrawTotals();
-    if (!draw_totals(sc->draws, sc->draw_count, tot))
-        return set_error(SOC_E_SHAPE, "%s: more than 2^31 - 1 triangles or transformed vertices", pass);
-    return SOC_OK;
-}
-
-// check_draw_scene, then the build record of the workspace: only a scene whose build succeeded, unchanged since.
-int check_built_scene(const soc_draw_scene* sc, const char* pass, bool attributes, DrawTotals& tot) {
-    int rc = check_draw_scene(sc, pass, attributes, tot);
-    if (rc) return rc;
-    DrawBuilt b{};
-    {
-        std::lock_guard<std::mutex> lock(g_draws_mutex);
-        const auto it = g_draws_built.find(sc->workspace);
-        if (it == g_draws_built.end())
-            return set_error(SOC_E_INVALID_ARG, "%s: the scene's workspace was not built (soc_draw_scene_build)", pass);
-        b = it->second;
-    }
-    if (b.fingerprint != draw_fingerprint(sc))
-        return set_error(SOC_E_INVALID_ARG, "%s: the draws, indices or uvs changed since soc_draw_scene_build", pass);
-    if (b.failed_draw != DRAWS_OK)
-        return set_error(SOC_E_SHAPE, "%s: the scene failed its build: draw %u fetches an index outside its vertex range", pass,
-                         b.failed_draw);
-    return SOC_OK;
-}
-
-int launch_raster_draws(const soc_draw_scene* sc, const DrawTotals& tot, int view, RasterParams p, void* target, size_t pitch,
-                        hipStream_t s, const char* pass) {
+RasterSource draws_source(const soc_draw_scene* sc, const DrawTotals& tot, int view) {
     const DrawWorkspace dw = draw_carve(sc->workspace, tot.slots, tot.triangles, sc->draw_count);
-    const int S = (int)tot.slots, T = (int)tot.triangles;
-    p.vertex_count = S;
-    p.triangle_count = T;
-    Workspace ws = carve(dw.view[view], S, T);
-    launch("raster_setup_draws", kWorkgroup, raster_setup_draws, ceil_div(max(S, 1), 256), kWorkgroup, 0, s, sc->positions,
-           dw.slots, sc->transforms, ws, p);
-    if (T > 0) {
-        launch("raster_small", kWorkgroup, raster_small, ceil_div(T, 256), kWorkgroup, 0, s, dw.indices, ws, p, target, pitch);
-        launch("raster_big", kWorkgroup, raster_big, 2048, kWorkgroup, 0, s, dw.indices, ws, p, target, pitch);
+    return RasterSource{sc->positions, nullptr, dw.indices, (int)tot.slots, (int)tot.triangles, dw.view[view], dw.slots, sc->transforms};
+}
+
+// The vertex kernel, raster_small and raster_big into a W x H target: the visibility buffer (bias null) or, depth-only, a
+// D32 image with the Vulkan depth bias {constant, slope}.
+int issue_raster(const RasterSource& src, const float* vp, int cull, void* target, size_t pitch, int W, int H, const float* bias,
+                 hipStream_t s, const char* pass) {
+    // model, vp, width, height, vertex_count, triangle_count, cull, depth_only, bias_constant, bias_slope, small_pixels
+    const RasterParams p{src.model ? mat4(src.model) : Mat4{}, mat4(vp), W, H, src.V, src.T, cull, bias ? 1 : 0,
+                         bias ? bias[0] : 0.0f, bias ? bias[1] : 0.0f, SMALL_PIXELS};
+    Workspace ws = carve(src.workspace, src.V, src.T);
+    const unsigned blocks = ceil_div(max(src.V, 1), 256);
+    if (!src.slots) launch("raster_setup", kWorkgroup, raster_setup, blocks, kWorkgroup, 0, s, src.positions, ws, p);
+    else launch("raster_setup_draws", kWorkgroup, raster_setup_draws, blocks, kWorkgroup, 0, s, src.positions, src.slots, src.transforms, ws, p);
+    if (src.T > 0) {
+        launch("raster_small", kWorkgroup, raster_small, ceil_div(src.T, 256), kWorkgroup, 0, s, src.indices, ws, p, target, pitch);
+        launch("raster_big", kWorkgroup, raster_big, 2048, kWorkgroup, 0, s, src.indices, ws, p, target, pitch);
     }
     return check_launch(pass);
 }
 
-}  // namespace
-}  // namespace soc
+struct GBufferImages { soc_img depth, albedo, emissive, normal, velocity; };
 
-using namespace soc;
-
-extern "C" size_t soc_raster_workspace_size(int32_t vertex_count, int32_t triangle_count) {
-    if (vertex_count < 0 || triangle_count < 0) return 0;
-    return align_up(align_up((size_t)vertex_count * 16, 256) + 256 + (size_t)triangle_count * 8, 256) +
-           (size_t)vertex_count * 64;
-}
-
-extern "C" int soc_raster_visibility(const soc_mesh* mesh, const float view_projection[16], int32_t cull,
-                                     uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
-                                     void* workspace, soc_stream stream) {
-    int rc = check_mesh(mesh, "soc_raster_visibility", false);
-    if (rc) return rc;
-    if (!view_projection || !visibility || !workspace || width <= 0 || height <= 0 || cull < 0 || cull > 2)
-        return set_error(SOC_E_INVALID_ARG, "soc_raster_visibility: null argument, bad extent or cull mode");
-    hipStream_t s = hs(stream);
-    if (clear) {
-        const size_t n = (size_t)width * height;
-        launch("raster_clear_vis", kWorkgroup, raster_clear_vis, (unsigned)((n + 255) / 256), kWorkgroup, 0, s, reinterpret_cast<unsigned long long*>(visibility), n);
-    }
-    RasterParams p = make_raster_params(mesh, view_projection, width, height, cull);
-    return launch_raster(mesh, p, visibility, (size_t)width * 8, workspace, s, "raster_visibility");
-}
-
-extern "C" int soc_raster_depth(const soc_mesh* mesh, const float view_projection[16], int32_t cull, float bias_constant,
-                                float bias_slope, soc_img depth, void* workspace, soc_stream stream) {
-    int rc = check_mesh(mesh, "soc_raster_depth", false);
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "soc_raster_depth", "depth");
-    if (rc) return rc;
-    if (!view_projection || !workspace || cull < 0 || cull > 2)
-        return set_error(SOC_E_INVALID_ARG, "soc_raster_depth: null argument or bad cull mode");
-    hipStream_t s = hs(stream);
-    // depth clear 1.0 (sun_shadow_draw.inl:71-74): the width texels of each row only, a padded view's bytes between
-    // the rows belong to the caller
-    launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)), kWorkgroup, 0, s,
-           static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
-    RasterParams p = make_raster_params(mesh, view_projection, depth.width, depth.height, cull);
-    p.depth_only = 1;
-    p.bias_constant = bias_constant;
-    p.bias_slope = bias_slope;
-    return launch_raster(mesh, p, depth.data, (size_t)depth.pitch_bytes, workspace, s, "raster_depth");
-}
-
-// The checks, parameters and launch geometry soc_gbuffer_resolve and soc_gbuffer_resolve_draws share: everything of
-// ResolveParams but the matrices of the mesh (model, normal3) and its triangle count.
-static int resolve_prepare(const char* pass, const soc_globals* g, const soc_material* d_materials, int32_t material_count,
-                           const uint64_t* visibility, const soc_img& depth, const soc_img& albedo, const soc_img& emissive,
-                           const soc_img& normal, const soc_img& velocity, ResolveParams& p, dim3& grd) {
-    int rc = check_img(depth, SOC_FMT_D32F, pass, "depth");
-    if (!rc) rc = check_img(albedo, SOC_FMT_RGBA16F, pass, "albedo");
-    if (!rc) rc = check_img(emissive, SOC_FMT_RGBA16F, pass, "emissive");
-    if (!rc) rc = check_img(normal, SOC_FMT_RGBA16F, pass, "normal");
-    if (!rc) rc = check_img(velocity, SOC_FMT_RGBA16F, pass, "velocity");
+// The checks, parameters and launch geometry every resolve shares: everything of ResolveParams but the matrices of the
+// mesh (model, normal3) and its triangle count.
+int resolve_prepare(const char* pass, const soc_globals* g, const soc_material* d_materials, int32_t material_count,
+                    const uint64_t* visibility, const GBufferImages& im, ResolveParams& p, dim3& grd) {
+    const soc_img* colour[4] = {&im.albedo, &im.emissive, &im.normal, &im.velocity};
+    const char* what[4] = {"albedo", "emissive", "normal", "velocity"};
+    int rc = check_img(im.depth, SOC_FMT_D32F, pass, "depth");
+    for (int i = 0; i < 4 && !rc; ++i) rc = check_img(*colour[i], SOC_FMT_RGBA16F, pass, what[i]);
     if (rc) return rc;
     if (!g || !d_materials || material_count <= 0 || !visibility)
         return set_error(SOC_E_INVALID_ARG, "%s: null globals / materials / visibility", pass);
-    const int W = depth.width, H = depth.height;
-    for (const soc_img* im : {&albedo, &emissive, &normal, &velocity})
-        if (im->width != W || im->height != H)
+    const int W = im.depth.width, H = im.depth.height;
+    for (const soc_img* i : colour)
+        if (i->width != W || i->height != H)
             return set_error(SOC_E_SHAPE, "%s: G-buffer images must share the depth extent", pass);
     p.vp = mat4(g->camera_projection_view_matrix);
     p.prev_vp = mat4(g->camera_previous_projection_view_matrix);
@@ -1430,6 +944,81 @@ static int resolve_prepare(const char* pass, const soc_globals* g, const soc_mat
     else if (p.wave_shape != 0 && p.wave_shape != 1) return set_error(SOC_E_INVALID_ARG, "%s: SOC_GB_WAVE %d", pass, p.wave_shape);
     return SOC_OK;
 }
+void set_mesh_matrices(ResolveParams& p, const soc_mesh* mesh) {
+    p.model = mat4(mesh->model_matrix);
+    p.normal3 = normal3_of(mesh->normal_matrix);
+    p.triangle_count = mesh->triangle_count;
+}
+
+// Who computes the per-vertex data the resolve reads: gbuffer_vertex_setup over a mesh (slots null), its draws form per
+// slot, or that one's motion form (previous: last frame's transforms). vdata null: nobody, the resolve computes
+// vertex_data inline (PRE = false).
+struct VertexStage {
+    soc_mesh src;   // the vertex arrays
+    int count;      // vertices or slots
+    float4* vdata;
+    const uint2* slots;
+    const soc_transform *transforms, *previous;
+};
+VertexStage mesh_stage(const soc_mesh* mesh, void* workspace) {
+    float4* vdata = workspace ? carve(workspace, mesh->vertex_count, mesh->triangle_count).vdata : nullptr;
+    return VertexStage{*mesh, mesh->vertex_count, vdata, nullptr, nullptr, nullptr};
+}
+
+// The vertex stage, then gbuffer_resolve<PRE, LAYER> over `mesh` (what the pixels read: indices, uvs, materials).
+int issue_resolve(const char* pass, const VertexStage& vs, const soc_mesh& mesh, bool layer, const soc_material* d_materials,
+                  const uint64_t* visibility, const GBufferImages& im, const ResolveParams& p, dim3 grd, hipStream_t s) {
+    const bool stage = vs.vdata && vs.count > 0;
+    const unsigned blocks = ceil_div(max(vs.count, 1), 256);
+    if (stage && !vs.slots)
+        launch("gbuffer_vertex_setup", kWorkgroup, gbuffer_vertex_setup, blocks, kWorkgroup, 0, s, vs.src, vs.vdata, p);
+    else if (stage && vs.previous)
+        launch("gbuffer_vertex_setup_draws_motion", kWorkgroup, gbuffer_vertex_setup_draws_motion, blocks, kWorkgroup, 0, s, vs.src,
+               vs.slots, vs.transforms, vs.previous, vs.count, vs.vdata, p);
+    else if (stage)
+        launch("gbuffer_vertex_setup_draws", kWorkgroup, gbuffer_vertex_setup_draws, blocks, kWorkgroup, 0, s, vs.src, vs.slots,
+               vs.transforms, vs.count, vs.vdata, p);
+    // named in the order the three kernels have always been emitted in (this compiler follows the first naming)
+    auto* kernel = gbuffer_resolve<true, false>;
+    if (!vs.vdata) kernel = gbuffer_resolve<false, false>;
+    else if (layer) kernel = gbuffer_resolve<true, true>;
+    launch(layer ? "gbuffer_resolve_layer" : "gbuffer_resolve", kWorkgroup, kernel, grd, dim3(64, 4), 0, s, mesh, d_materials,
+           reinterpret_cast<const unsigned long long*>(visibility), dimg(im.depth), dimg(im.albedo), dimg(im.emissive),
+           dimg(im.normal), dimg(im.velocity), vs.vdata, p);
+    return check_launch(pass);
+}
+
+}  // namespace
+}  // namespace soc
+
+using namespace soc;
+
+extern "C" int soc_raster_visibility(const soc_mesh* mesh, const float view_projection[16], int32_t cull,
+                                     uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
+                                     void* workspace, soc_stream stream) {
+    int rc = check_mesh(mesh, "soc_raster_visibility", false);
+    if (rc) return rc;
+    if (!view_projection || !visibility || !workspace || width <= 0 || height <= 0 || cull < 0 || cull > 2)
+        return set_error(SOC_E_INVALID_ARG, "soc_raster_visibility: null argument, bad extent or cull mode");
+    hipStream_t s = hs(stream);
+    if (clear) clear_visibility(visibility, width, height, s);
+    return issue_raster(mesh_source(mesh, workspace), view_projection, cull, visibility, (size_t)width * 8, width, height, nullptr,
+                        s, "raster_visibility");
+}
+
+extern "C" int soc_raster_depth(const soc_mesh* mesh, const float view_projection[16], int32_t cull, float bias_constant,
+                                float bias_slope, soc_img depth, void* workspace, soc_stream stream) {
+    int rc = check_mesh(mesh, "soc_raster_depth", false);
+    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "soc_raster_depth", "depth");
+    if (rc) return rc;
+    if (!view_projection || !workspace || cull < 0 || cull > 2)
+        return set_error(SOC_E_INVALID_ARG, "soc_raster_depth: null argument or bad cull mode");
+    hipStream_t s = hs(stream);
+    clear_depth(depth, s);
+    const float bias[2] = {bias_constant, bias_slope};
+    return issue_raster(mesh_source(mesh, workspace), view_projection, cull, depth.data, (size_t)depth.pitch_bytes, depth.width,
+                        depth.height, bias, s, "raster_depth");
+}
 
 extern "C" int soc_gbuffer_resolve(const soc_globals* g, const soc_mesh* mesh, const soc_material* d_materials,
                                    int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
@@ -1437,28 +1026,14 @@ extern "C" int soc_gbuffer_resolve(const soc_globals* g, const soc_mesh* mesh, c
                                    soc_stream stream) {
     int rc = check_mesh(mesh, "soc_gbuffer_resolve", true);
     if (rc) return rc;
+    const GBufferImages im{depth, albedo, emissive, normal, velocity};
     ResolveParams p{};
-    dim3 blk(64, 4), grd;
-    rc = resolve_prepare("soc_gbuffer_resolve", g, d_materials, material_count, visibility, depth, albedo, emissive, normal,
-                         velocity, p, grd);
+    dim3 grd;
+    rc = resolve_prepare("soc_gbuffer_resolve", g, d_materials, material_count, visibility, im, p, grd);
     if (rc) return rc;
-    p.model = mat4(mesh->model_matrix);
-    const float* nm = mesh->normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
-    const float n3[9] = {nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]};
-    for (int i = 0; i < 9; ++i) p.normal3.m[i] = n3[i];
-    p.triangle_count = mesh->triangle_count;
-    const unsigned long long* vis = reinterpret_cast<const unsigned long long*>(visibility);
-    if (workspace) {   // per-vertex outputs once, then the per-pixel resolve reads them
-        const Workspace ws = carve(workspace, mesh->vertex_count, mesh->triangle_count);
-        if (mesh->vertex_count > 0)
-            launch("gbuffer_vertex_setup", kWorkgroup, gbuffer_vertex_setup, ceil_div(mesh->vertex_count, 256), kWorkgroup, 0, hs(stream), *mesh, ws.vdata, p);
-        launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true, false>, grd, blk, 0, hs(stream), *mesh, d_materials, vis, dimg(depth), dimg(albedo),
-                                                           dimg(emissive), dimg(normal), dimg(velocity), ws.vdata, p);
-    } else {
-        launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<false, false>, grd, blk, 0, hs(stream), *mesh, d_materials, vis, dimg(depth), dimg(albedo),
-                                                            dimg(emissive), dimg(normal), dimg(velocity), nullptr, p);
-    }
-    return check_launch("gbuffer_resolve");
+    set_mesh_matrices(p, mesh);
+    // with a workspace: per-vertex outputs once, then the per-pixel resolve reads them
+    return issue_resolve("gbuffer_resolve", mesh_stage(mesh, workspace), *mesh, false, d_materials, visibility, im, p, grd, hs(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1471,32 +1046,23 @@ extern "C" int soc_draw_terrain(const soc_globals* g, const soc_mesh* mesh, cons
     int rc = check_mesh(mesh, name, true);
     if (rc) return rc;
     if (!workspace) return set_error(SOC_E_INVALID_ARG, "%s: null workspace (the layer always uses the per-vertex workspace)", name);
+    // DrawTerrain has no emissive attachment (draw_terrain.inl:14-17): the albedo stands in, for the shared checks and in
+    // the launch (the LAYER form never touches it)
+    const GBufferImages im{depth, albedo, albedo, normal, velocity};
     ResolveParams p{};
-    dim3 blk(64, 4), grd;
-    // DrawTerrain has no emissive attachment (draw_terrain.inl:14-17): the albedo stands in for it in the shared checks
-    rc = resolve_prepare(name, g, d_materials, material_count, visibility, depth, albedo, albedo, normal, velocity, p, grd);
+    dim3 grd;
+    rc = resolve_prepare(name, g, d_materials, material_count, visibility, im, p, grd);
     if (rc) return rc;
+    // the layer always runs 8 x 8-pixel waves, whatever SOC_GB_WAVE asked for
     p.wave_shape = 2;
     grd = dim3(ceil_div(depth.width, 32), ceil_div(depth.height, 8));
-    p.model = mat4(mesh->model_matrix);
-    const float* nm = mesh->normal_matrix;   // f32mat3x3(normal_matrix): upper 3x3, column-major
-    const float n3[9] = {nm[0], nm[1], nm[2], nm[4], nm[5], nm[6], nm[8], nm[9], nm[10]};
-    for (int i = 0; i < 9; ++i) p.normal3.m[i] = n3[i];
-    p.triangle_count = mesh->triangle_count;
+    set_mesh_matrices(p, mesh);
     hipStream_t s = hs(stream);
-    const int W = depth.width, H = depth.height;
-    const size_t n = (size_t)W * H;
-    unsigned long long* vis = reinterpret_cast<unsigned long long*>(visibility);
-    launch("raster_clear_vis", kWorkgroup, raster_clear_vis, (unsigned)((n + 255) / 256), kWorkgroup, 0, s, vis, n);
-    const RasterParams rp = make_raster_params(mesh, g->camera_projection_view_matrix, W, H, SOC_CULL_FRONT);
-    rc = launch_raster(mesh, rp, visibility, (size_t)W * 8, workspace, s, "draw_terrain");
+    clear_visibility(visibility, depth.width, depth.height, s);
+    rc = issue_raster(mesh_source(mesh, workspace), g->camera_projection_view_matrix, SOC_CULL_FRONT, visibility,
+                      (size_t)depth.width * 8, depth.width, depth.height, nullptr, s, "draw_terrain");
     if (rc) return rc;
-    const Workspace ws = carve(workspace, mesh->vertex_count, mesh->triangle_count);
-    if (mesh->vertex_count > 0)
-        launch("gbuffer_vertex_setup", kWorkgroup, gbuffer_vertex_setup, ceil_div(mesh->vertex_count, 256), kWorkgroup, 0, s, *mesh, ws.vdata, p);
-    launch("gbuffer_resolve_layer", kWorkgroup, gbuffer_resolve<true, true>, grd, blk, 0, s, *mesh, d_materials, vis, dimg(depth),
-           dimg(albedo), dimg(albedo), dimg(normal), dimg(velocity), ws.vdata, p);
-    return check_launch("draw_terrain");
+    return issue_resolve("draw_terrain", mesh_stage(mesh, workspace), *mesh, true, d_materials, visibility, im, p, grd, s);
 }
 
 extern "C" int soc_sun_shadow_draw_terrain(const soc_mesh* mesh, const float view_projection[16], int32_t clear, soc_img depth,
@@ -1507,31 +1073,15 @@ extern "C" int soc_sun_shadow_draw_terrain(const soc_mesh* mesh, const float vie
     if (rc) return rc;
     if (!view_projection || !workspace) return set_error(SOC_E_INVALID_ARG, "%s: null view_projection or workspace", name);
     hipStream_t s = hs(stream);
-    if (clear)   // a frame whose head draws no shadow: the clear SunShadowDraw would have made (sun_shadow_draw.inl:71-74)
-        launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)), kWorkgroup, 0, s,
-               static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
-    // sun_shadow_draw_terrain.inl:47-58: cull BACK and no depth bias (bias_constant = bias_slope = 0, as zero-initialised)
-    RasterParams p = make_raster_params(mesh, view_projection, depth.width, depth.height, SOC_CULL_BACK);
-    p.depth_only = 1;
-    return launch_raster(mesh, p, depth.data, (size_t)depth.pitch_bytes, workspace, s, "sun_shadow_draw_terrain");
+    if (clear) clear_depth(depth, s);   // a frame whose head draws no shadow: the clear SunShadowDraw would have made
+    const float no_bias[2] = {0.0f, 0.0f};   // sun_shadow_draw_terrain.inl:47-58: cull BACK and no depth bias
+    return issue_raster(mesh_source(mesh, workspace), view_projection, SOC_CULL_BACK, depth.data, (size_t)depth.pitch_bytes,
+                        depth.width, depth.height, no_bias, s, "sun_shadow_draw_terrain");
 }
 
 // ------------------------------------------------------------------------------------------------
 // Draw scenes: entry points
 // ------------------------------------------------------------------------------------------------
-extern "C" size_t soc_draw_workspace_size(const soc_draw* draws, int32_t draw_count) {
-    DrawTotals t;
-    if (!draw_totals(draws, draw_count, t)) return 0;
-    return draw_tables_bytes(t.slots, t.triangles, draw_count) +
-           2 * align_up(soc_raster_workspace_size((int32_t)t.slots, (int32_t)t.triangles), 256);
-}
-
-extern "C" void soc_draw_scene_release(const soc_draw_scene* scene) {
-    if (!scene || !scene->workspace) return;
-    std::lock_guard<std::mutex> lock(g_draws_mutex);
-    g_draws_built.erase(scene->workspace);
-}
-
 extern "C" int soc_draw_scene_build(const soc_draw_scene* scene, soc_stream stream) {
     DrawTotals tot;
     int rc = check_draw_scene(scene, "soc_draw_scene_build", false, tot);
@@ -1565,10 +1115,7 @@ extern "C" int soc_draw_scene_build(const soc_draw_scene* scene, soc_stream stre
         (void)hipGetLastError();
         return set_error(SOC_E_HIP, "soc_draw_scene_build: copying the draw tables or reading the validation flag failed");
     }
-    {
-        std::lock_guard<std::mutex> lock(g_draws_mutex);
-        g_draws_built[scene->workspace] = DrawBuilt{draw_fingerprint(scene), failed};
-    }
+    record_built_scene(scene, failed);
     if (failed != DRAWS_OK) {
         const soc_draw& d = scene->draws[failed];
         return set_error(SOC_E_SHAPE, "soc_draw_scene_build: draw %u fetches an index that, with vertex_offset %d, lies outside "
@@ -1586,17 +1133,9 @@ extern "C" int soc_raster_visibility_draws(const soc_draw_scene* scene, const fl
     if (!view_projection || !visibility || width <= 0 || height <= 0 || cull < 0 || cull > 2)
         return set_error(SOC_E_INVALID_ARG, "soc_raster_visibility_draws: null argument, bad extent or cull mode");
     hipStream_t s = hs(stream);
-    if (clear) {
-        const size_t n = (size_t)width * height;
-        launch("raster_clear_vis", kWorkgroup, raster_clear_vis, (unsigned)((n + 255) / 256), kWorkgroup, 0, s, reinterpret_cast<unsigned long long*>(visibility), n);
-    }
-    RasterParams p{};
-    p.vp = mat4(view_projection);
-    p.width = width;
-    p.height = height;
-    p.cull = cull;
-    p.small_pixels = SMALL_PIXELS;
-    return launch_raster_draws(scene, tot, 0, p, visibility, (size_t)width * 8, s, "raster_visibility_draws");
+    if (clear) clear_visibility(visibility, width, height, s);
+    return issue_raster(draws_source(scene, tot, 0), view_projection, cull, visibility, (size_t)width * 8, width, height, nullptr, s,
+                        "raster_visibility_draws");
 }
 
 extern "C" int soc_raster_depth_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
@@ -1608,32 +1147,23 @@ extern "C" int soc_raster_depth_draws(const soc_draw_scene* scene, const float v
     if (!view_projection || cull < 0 || cull > 2)
         return set_error(SOC_E_INVALID_ARG, "soc_raster_depth_draws: null argument or bad cull mode");
     hipStream_t s = hs(stream);
-    launch("raster_clear_depth", kWorkgroup, raster_clear_depth, dim3(ceil_div(depth.width, 256), min(depth.height, 65535)), kWorkgroup, 0, s,
-           static_cast<char*>(depth.data), (size_t)depth.pitch_bytes, depth.width, depth.height);
-    RasterParams p{};
-    p.vp = mat4(view_projection);
-    p.width = depth.width;
-    p.height = depth.height;
-    p.cull = cull;
-    p.small_pixels = SMALL_PIXELS;
-    p.depth_only = 1;
-    p.bias_constant = bias_constant;
-    p.bias_slope = bias_slope;
-    return launch_raster_draws(scene, tot, 1, p, depth.data, (size_t)depth.pitch_bytes, s, "raster_depth_draws");
+    clear_depth(depth, s);
+    const float bias[2] = {bias_constant, bias_slope};
+    return issue_raster(draws_source(scene, tot, 1), view_projection, cull, depth.data, (size_t)depth.pitch_bytes, depth.width,
+                        depth.height, bias, s, "raster_depth_draws");
 }
 
 // soc_gbuffer_resolve_draws (previous null) and soc_gbuffer_resolve_draws_motion: the same checks, tables and resolve; the
 // vertex stage is gbuffer_vertex_setup_draws or its motion form.
 static int resolve_draws(const char* name, const char* pass, const soc_globals* g, const soc_draw_scene* scene,
                          const soc_transform* previous, const soc_material* d_materials, int32_t material_count,
-                         const uint64_t* visibility, const soc_img& depth, const soc_img& albedo, const soc_img& emissive,
-                         const soc_img& normal, const soc_img& velocity, soc_stream stream) {
+                         const uint64_t* visibility, const GBufferImages& im, soc_stream stream) {
     DrawTotals tot;
     int rc = check_built_scene(scene, name, true, tot);
     if (rc) return rc;
-    ResolveParams p{};
-    dim3 blk(64, 4), grd;
-    rc = resolve_prepare(name, g, d_materials, material_count, visibility, depth, albedo, emissive, normal, velocity, p, grd);
+    ResolveParams p{};   // model and normal3 stay zero: the vertex stage takes each slot's from its transform
+    dim3 grd;
+    rc = resolve_prepare(name, g, d_materials, material_count, visibility, im, p, grd);
     if (rc) return rc;
     if (material_count < scene->material_count)
         return set_error(SOC_E_SHAPE, "%s: %d materials, the scene's draws name up to %d", name, material_count,
@@ -1641,7 +1171,6 @@ static int resolve_draws(const char* name, const char* pass, const soc_globals* 
     const int S = (int)tot.slots, T = (int)tot.triangles;
     p.triangle_count = T;
     const DrawWorkspace dw = draw_carve(scene->workspace, tot.slots, tot.triangles, scene->draw_count);
-    const Workspace ws = carve(dw.view[0], S, T);
     // the scene's vertex arrays for the vertex stage; the tables as one mesh for the resolve (it reads the indices, the
     // uvs by slot, the materials and the per-slot vertex data only)
     soc_mesh src{};
@@ -1654,24 +1183,15 @@ static int resolve_draws(const char* name, const char* pass, const soc_globals* 
     view.materials = dw.materials;
     view.vertex_count = S;
     view.triangle_count = T;
-    hipStream_t s = hs(stream);
-    if (S > 0 && previous)
-        launch("gbuffer_vertex_setup_draws_motion", kWorkgroup, gbuffer_vertex_setup_draws_motion, ceil_div(S, 256), kWorkgroup, 0,
-               s, src, dw.slots, scene->transforms, previous, S, ws.vdata, p);
-    else if (S > 0)
-        launch("gbuffer_vertex_setup_draws", kWorkgroup, gbuffer_vertex_setup_draws, ceil_div(S, 256), kWorkgroup, 0, s, src, dw.slots,
-               scene->transforms, S, ws.vdata, p);
-    launch("gbuffer_resolve", kWorkgroup, gbuffer_resolve<true, false>, grd, blk, 0, s, view, d_materials,
-           reinterpret_cast<const unsigned long long*>(visibility), dimg(depth), dimg(albedo), dimg(emissive), dimg(normal),
-           dimg(velocity), ws.vdata, p);
-    return check_launch(pass);
+    const VertexStage vs{src, S, carve(dw.view[0], S, T).vdata, dw.slots, scene->transforms, previous};
+    return issue_resolve(pass, vs, view, false, d_materials, visibility, im, p, grd, hs(stream));
 }
 
 extern "C" int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene, const soc_material* d_materials,
                                          int32_t material_count, const uint64_t* visibility, soc_img depth, soc_img albedo,
                                          soc_img emissive, soc_img normal, soc_img velocity, soc_stream stream) {
     return resolve_draws("soc_gbuffer_resolve_draws", "gbuffer_resolve_draws", g, scene, nullptr, d_materials, material_count,
-                         visibility, depth, albedo, emissive, normal, velocity, stream);
+                         visibility, GBufferImages{depth, albedo, emissive, normal, velocity}, stream);
 }
 
 extern "C" int soc_gbuffer_resolve_draws_motion(const soc_globals* g, const soc_draw_scene* scene,
@@ -1682,5 +1202,5 @@ extern "C" int soc_gbuffer_resolve_draws_motion(const soc_globals* g, const soc_
     if (!previous_transforms)
         return set_error(SOC_E_INVALID_ARG, "soc_gbuffer_resolve_draws_motion: null previous_transforms");
     return resolve_draws("soc_gbuffer_resolve_draws_motion", "gbuffer_resolve_draws_motion", g, scene, previous_transforms,
-                         d_materials, material_count, visibility, depth, albedo, emissive, normal, velocity, stream);
+                         d_materials, material_count, visibility, GBufferImages{depth, albedo, emissive, normal, velocity}, stream);
 }

@@ -1,8 +1,9 @@
 // san_host — drives the host code under AddressSanitizer + UndefinedBehaviorSanitizer (tools/sanitize/Makefile).
 // No GPU call is made: the globals feed and ECS scene feed, ABI introspection, the render graph (construction,
-// caller passes, derived and ring dependencies, raster head, error paths), the clouds planner, the PNG / EXR writers, the scene
-// synthesiser, and every pass of the CPU oracle on small images (odd extents included). Exit 0 when every check
-// passes; a sanitizer report aborts the run (-fno-sanitize-recover).
+// caller passes, derived and ring dependencies, raster head, error paths), the clouds planner, the raster workspaces and
+// the draw scenes' host checks, the PNG / EXR writers, the scene synthesiser, and every pass of the CPU oracle on small
+// images (odd extents included). Exit 0 when every check passes; a sanitizer report aborts the run
+// (-fno-sanitize-recover).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -417,6 +418,120 @@ void oracle_raster(const soc_globals& g0, int W, int H) {
     std::vector<float> tde((size_t)W * H);
     expect(soc_scene_gbuffer(1, &g, W, H, tal.data(), tem.data(), tno.data(), tde.data(), tve.data()) == 0, "terrain gbuffer");
 }
+
+// Draw scenes and the raster workspaces (csrc/raster_host.cpp) over the paths that return before any HIP call: the two
+// size functions against hand-computed layouts, every rejection of tests/test_draws_abi.py's
+// test_host_validation_without_gpu with its code, and the release of scenes that were never built. The device pointers
+// are fake and never dereferenced; the draw lists are real host arrays, which the checks do read.
+soc_draw make_draw(int first_index, int triangles, int first_vertex, int vertices, int transform = 0, int material = 0) {
+    return soc_draw{first_index, triangles, 0, first_vertex, vertices, transform, material};
+}
+soc_draw_scene make_scene(const std::vector<soc_draw>& draws) {
+    const float* fake = reinterpret_cast<const float*>(256);
+    soc_draw_scene sc;
+    std::memset(&sc, 0, sizeof sc);
+    sc.positions = sc.normals = sc.uvs = fake;
+    sc.indices = reinterpret_cast<const uint32_t*>(256);
+    sc.transforms = reinterpret_cast<const soc_transform*>(256);
+    sc.workspace = reinterpret_cast<void*>(4096);
+    sc.draws = draws.data();
+    sc.draw_count = (int32_t)draws.size();
+    sc.vertex_count = sc.index_count = 30;
+    sc.transform_count = sc.material_count = 2;
+    return sc;
+}
+bool mentions(const char* word) { return std::strstr(soc_last_error_string(), word) != nullptr; }
+
+void draw_scenes(const soc_globals& g) {
+    // [3 float4 -> 256] [counter 256] [1 entry -> 256] [3 x 64 B of vertex data]
+    expect(soc_raster_workspace_size(3, 1) == 256 + 256 + 256 + 192, "raster workspace: 3 vertices, 1 triangle");
+    expect(soc_raster_workspace_size(30, 10) == 512 + 256 + 256 + 1920, "raster workspace: 30 vertices, 10 triangles");
+    expect(soc_raster_workspace_size(-1, 1) == 0 && soc_raster_workspace_size(1, -1) == 0, "raster workspace: negative counts");
+    const soc_draw ok = make_draw(0, 10, 0, 30, 1, 1);
+    // the flag's 256 B, five tables of no bytes, then two views of an empty raster workspace (its counter's 256 B)
+    expect(soc_draw_workspace_size(nullptr, 0) == 256 + 2 * 256, "draw workspace: empty list");
+    // flag 256, slots 240 -> 256, uvs 256, indices 120 -> 256, materials 40 -> 256, one DrawRec 36 -> 256, then two views
+    // of soc_raster_workspace_size(30, 10) = 2944 -> 3072
+    expect(soc_draw_workspace_size(&ok, 1) == 6 * 256 + 2 * 3072, "draw workspace: one draw");
+    expect(soc_draw_workspace_size(nullptr, 1) == 0 && soc_draw_workspace_size(&ok, -1) == 0, "draw workspace: null list, negative count");
+    for (const soc_draw& bad : {make_draw(0, -1, 0, 30), make_draw(0, 10, 0, -30), make_draw(0, 10, -1, 30), make_draw(-3, 10, 0, 30)})
+        expect(soc_draw_workspace_size(&bad, 1) == 0, "draw workspace: negative field");
+    const soc_draw big[2] = {make_draw(0, 0x7FFFFFFF, 0, 3), make_draw(0, 0x7FFFFFFF, 0, 3)};
+    expect(soc_draw_workspace_size(big, 2) == 0, "draw workspace: totals beyond int32");
+
+    const std::vector<soc_draw> one{ok};
+    expect(soc_draw_scene_build(nullptr, nullptr) == SOC_E_INVALID_ARG && mentions("soc_draw_scene_build"), "build: null scene");
+    for (int field = 0; field < 4; ++field) {
+        soc_draw_scene sc = make_scene(one);
+        if (field == 0) sc.positions = nullptr;
+        if (field == 1) sc.indices = nullptr;
+        if (field == 2) sc.transforms = nullptr;
+        if (field == 3) sc.workspace = nullptr;
+        expect(soc_draw_scene_build(&sc, nullptr) == SOC_E_INVALID_ARG && mentions("soc_draw_scene_build"), "build: null field");
+    }
+    for (int k = 0; k < 7; ++k) {
+        soc_draw_scene sc = make_scene(one);
+        if (k == 0) sc.vertex_count = -1;
+        if (k == 1) sc.index_count = -1;
+        if (k == 2) sc.draw_count = -1;
+        if (k == 3) sc.transform_count = 0;
+        if (k == 4) sc.material_count = 0;
+        if (k == 5) sc.workspace = reinterpret_cast<void*>(4096 + 64);
+        if (k == 6) sc.draws = nullptr;
+        expect(soc_draw_scene_build(&sc, nullptr) == SOC_E_INVALID_ARG, "build: bad count, misaligned workspace or null draws");
+    }
+    for (const soc_draw& bad : {make_draw(0, -1, 0, 30), make_draw(-1, 10, 0, 30), make_draw(0, 10, -1, 30), make_draw(0, 10, 0, -1)}) {
+        const std::vector<soc_draw> ds{ok, bad};
+        const soc_draw_scene sc = make_scene(ds);
+        expect(soc_draw_scene_build(&sc, nullptr) == SOC_E_INVALID_ARG && mentions("draw 1"), "build: negative draw field");
+    }
+    const soc_draw beyond_indices = make_draw(3, 10, 0, 30);   // 3 + 30 > 30
+    const struct { const char* word; soc_draw bad; } shapes[] = {
+        {"index_count", beyond_indices},
+        {"vertex_count", make_draw(0, 10, 1, 30)},   // [1, 31) outside 30 vertices
+        {"transform", make_draw(0, 10, 0, 30, 2)},
+        {"material", make_draw(0, 10, 0, 30, 0, 2)}};
+    for (const auto& c : shapes) {
+        const std::vector<soc_draw> ds{ok, ok, c.bad};
+        const soc_draw_scene sc = make_scene(ds);
+        expect(soc_draw_scene_build(&sc, nullptr) == SOC_E_SHAPE && mentions("draw 2") && mentions(c.word) &&
+                   mentions("soc_draw_scene_build"), "build: draw outside its arrays");
+    }
+    {
+        const std::vector<soc_draw> ds{make_draw(0, 10, 0, 30, -1)};
+        const soc_draw_scene sc = make_scene(ds);
+        expect(soc_draw_scene_build(&sc, nullptr) == SOC_E_SHAPE && mentions("draw 0"), "build: negative transform");
+        // 0xFFFFFFFE triangles or more (draws may share an index range): the visibility key cannot hold their ids
+        const std::vector<soc_draw> huge(7, make_draw(0, 0x7FFFFFFF / 3, 0, 3));
+        soc_draw_scene hs = make_scene(huge);
+        hs.index_count = 0x7FFFFFFF;
+        expect(soc_draw_scene_build(&hs, nullptr) == SOC_E_SHAPE && mentions("too many triangles"), "build: too many triangles");
+    }
+    // the per-frame entry points make the same checks, then refuse a workspace that was never built: no launch
+    float vp[16] = {0};
+    HostImg depth(64, 36, SOC_FMT_D32F, 4), a(64, 36, SOC_FMT_RGBA16F, 8);
+    std::vector<uint64_t> vis(64 * 36);
+    const soc_material* mats = reinterpret_cast<const soc_material*>(256);
+    const std::vector<soc_draw> out_of_range{ok, ok, beyond_indices};
+    const soc_draw_scene unbuilt = make_scene(one), bad_scene = make_scene(out_of_range);
+    for (int call = 0; call < 3; ++call) {
+        const char* name = call == 0 ? "soc_raster_visibility_draws" : call == 1 ? "soc_raster_depth_draws" : "soc_gbuffer_resolve_draws";
+        auto run = [&](const soc_draw_scene* sc) {
+            if (call == 0) return soc_raster_visibility_draws(sc, vp, 1, vis.data(), 64, 36, 1, nullptr);
+            if (call == 1) return soc_raster_depth_draws(sc, vp, 2, 1.25f, 1.75f, depth.img, nullptr);
+            return soc_gbuffer_resolve_draws(&g, sc, mats, 2, vis.data(), depth.img, a.img, a.img, a.img, a.img, nullptr);
+        };
+        expect(run(nullptr) == SOC_E_INVALID_ARG && mentions(name), "per-frame: null scene");
+        expect(run(&bad_scene) == SOC_E_SHAPE && mentions(name) && mentions("draw 2"), "per-frame: draw outside its arrays");
+        expect(run(&unbuilt) == SOC_E_INVALID_ARG && mentions(name) && mentions("not built"), "per-frame: never built");
+    }
+    soc_draw_scene no_normals = make_scene(one);
+    no_normals.normals = nullptr;
+    expect(soc_gbuffer_resolve_draws(&g, &no_normals, mats, 2, vis.data(), depth.img, a.img, a.img, a.img, a.img, nullptr) ==
+               SOC_E_INVALID_ARG && mentions("normals"), "per-frame: resolve without normals");
+    soc_draw_scene_release(nullptr);
+    soc_draw_scene_release(&unbuilt);   // an unknown workspace: no-op
+}
 }  // namespace
 
 int main() {
@@ -430,6 +545,7 @@ int main() {
         writers(W, H);
         oracle_frame(g, W, H);
         oracle_raster(g, W, H);
+        draw_scenes(g);
     }
     for (float v : {0.0f, 1e-8f, 0.5f, 1.0f, 65504.0f, 1e9f, -3.0f, INFINITY, NAN})
         (void)soc_oracle_f16_to_f32(soc_oracle_f32_to_f16(v));
