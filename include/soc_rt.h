@@ -403,6 +403,46 @@ int soc_tone_mapping(const soc_globals* g, soc_img color, const soc_auto_exposur
 /* Device copy of the globals block (the reference's per-frame UBO upload, renderer.cpp:648-657). */
 int soc_upload_globals(const soc_globals* g, soc_globals* d_globals, soc_stream stream);
 
+/* --- Bounded lights (opt-in) ------------------------------------------------------
+ * The reference's lights reach everywhere (1/d^2 never ends), so every pixel pays for every light. A caller may give
+ * each light a range r (0: unlimited, as the reference; else finite and > 0), indexed like the globals' point_lights /
+ * spot_lights (soc_scene_update appends the lights in entity order per kind). A ranged light's contribution is
+ * multiplied by w = clamp(1 - (d^2 / r^2)^2, 0, 1) (KHR_lights_punctual's window), and with f = w for a point light,
+ * f = w * the cone term for a spot light (the cone term alone for an unlimited one), a light contributes to a pixel
+ * only where f > 0: elsewhere it contributes nothing, a NaN or Inf term included (the unbounded calls add NaN * 0
+ * outside a spot's cone where the normal is not unit). An unlimited point light is exactly the unbounded one: a
+ * bounded call whose ranges are all 0 and which has no spot lights gives soc_composition's bits.
+ * A range so large that 1 / r^2 is below fp32 acts as unlimited; one so small that it is above fp32 is clamped. */
+typedef struct soc_light_bounds {
+    float point_range[SOC_MAX_POINT_LIGHTS];
+    float spot_range[SOC_MAX_SPOT_LIGHTS];
+} soc_light_bounds;
+/* Bytes of the DEVICE record the bounded kernels read (the library's own layout, not soc_light_bounds). */
+#define SOC_LIGHT_BOUNDS_DEVICE_BYTES 2048
+/* Validates every range (negative, NaN or Inf: SOC_E_INVALID_ARG naming the first bad index, before any HIP call),
+ * then writes the device record to d_bounds, stream-ordered like soc_upload_globals (the host struct is consumed
+ * before the call returns). */
+int soc_upload_light_bounds(const soc_light_bounds* host, void* d_bounds, soc_stream stream);
+/* SOC_LIGHTS_CULL: on the pair path each wave tests the lights against the box of its 16x8 patch's lit pixels first and
+ * runs its loops over the lights that may reach it; the result is bit-identical to the call without the flag (the test
+ * is conservative against the per-pixel test as the device computes it, csrc/light_cull.hpp). Ignored off the pair
+ * path (odd widths, misaligned views). */
+#define SOC_LIGHTS_CULL 1u
+/* soc_composition / soc_composition_luminance_histogram with bounded lights. d_bounds (soc_upload_light_bounds) must not
+ * be NULL. d_shaded_pairs (device u32, may be NULL; measuring only: it selects kernels that pay one atomic per wave):
+ * on the pair path every wave with a lit pixel adds the number of lights its loops ran (all of them without
+ * SOC_LIGHTS_CULL); untouched off the pair path. */
+int soc_composition_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                            soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                            soc_img clouds, const void* d_bounds, uint32_t flags, uint32_t* d_shaded_pairs,
+                            soc_stream stream);
+int soc_composition_luminance_histogram_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target,
+                                                soc_img albedo, soc_img emissive, soc_img normal, soc_img depth,
+                                                soc_img ssao, soc_img shadow, soc_img clouds,
+                                                soc_auto_exposure* d_auto_exposure, uint32_t* scratch,
+                                                const void* d_bounds, uint32_t flags, uint32_t* d_shaded_pairs,
+                                                soc_stream stream);
+
 /* --- Render graph (host C++ mirror of Renderer::rebuild_task_graph, renderer.cpp:929-1235) ------ */
 
 /* Frame images. The caller allocates them (device memory) and keeps them alive. */
@@ -494,6 +534,10 @@ void soc_renderer_destroy(soc_renderer* r);
 int soc_renderer_execute(soc_renderer* r, const soc_globals* g, int32_t phase, soc_stream stream);
 /* Histogram normalisation for a multi-GPU resolve: total pixels over all ranks (0 = this frame). */
 int soc_renderer_set_exposure_pixels(soc_renderer* r, uint64_t total_pixels, int32_t wide_accumulator);
+/* Composition with bounded lights (above) in either histogram mode: d_bounds is the device record the caller rewrites
+ * between frames on its stream (soc_upload_light_bounds), like every frame input; flags: SOC_LIGHTS_*. NULL removes
+ * the setting. The pass's declared uses, the graph and the frame plan are unchanged. */
+int soc_renderer_set_light_bounds(soc_renderer* r, const void* d_bounds, uint32_t flags);
 int32_t soc_renderer_pass_count(const soc_renderer* r);
 const char* soc_renderer_pass_name(const soc_renderer* r, int32_t index);
 const char* soc_renderer_pass_group(const soc_renderer* r, int32_t index);   /* renderer.cpp:558-588 names */

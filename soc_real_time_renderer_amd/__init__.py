@@ -30,6 +30,7 @@ __all__ = ["SocError", "lib", "img", "Globals", "Camera", "AutoExposure", "globa
            "ssao_blur", "screen_space_reflection", "DepthOfFieldChain", "depth_of_field_chain", "depth_of_field_mips",
            "depth_of_field", "cloud_rendering", "composition", "generate_luminance_histogram",
            "resolve_luminance_histogram", "temporal_antialiasing", "copy_image", "tone_mapping", "upload_globals",
+           "light_bounds", "light_bounds_device_buffer", "upload_light_bounds",
            "Renderer", "read_image", "write_png", "write_exr", "FMT_RGBA16F", "FMT_D32F", "FMT_R8_UNORM", "FMT_RGBA8_UNORM", "FMT_RGBA8_SRGB",
            "FMT_RGBA32F", "PHASE_PRE_EXPOSURE", "PHASE_POST_EXPOSURE", "PHASE_ALL"]
 
@@ -155,7 +156,8 @@ def entity(position=(0.0, 0.0, 0.0), rotation=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 
 
 def scene_update(g: Globals, entities):
     """Scene::update (scene.cpp:47-118): fills g's light lists; returns the (N, 4, 4) model and normal matrices
-    (row index = glm column, i.e. m[c][r] like glm)."""
+    (row index = glm column, i.e. m[c][r] like glm). Ranges for light_bounds() are given in the order this feed emits
+    the lights, which is entity order per kind."""
     n = len(entities)
     arr = (_abi.Entity * max(n, 1))(*entities)
     models = np.zeros((max(n, 1), 16), np.float32)
@@ -330,9 +332,42 @@ def cloud_rendering(g, depth, noise, target, workspace=None, stream=None):
            "cloud_rendering")
 
 
-def composition(g, target, albedo, emissive, normal, depth, ssao, shadow, clouds, d_globals=None, stream=None):
-    _check(lib().soc_composition(_gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal),
-                                 img(depth), img(ssao), img(shadow), img(clouds), _stream(stream)), "composition")
+def light_bounds(point_ranges=(), spot_ranges=()) -> "_abi.LightBounds":
+    """soc_light_bounds from the ranges of the point and the spot lights, in the order of the globals' light lists
+    (missing entries and 0: unlimited, as the reference's lights)."""
+    b = _abi.LightBounds()
+    for dst, src, kind in ((b.point_range, point_ranges, "point"), (b.spot_range, spot_ranges, "spot")):
+        src = [float(v) for v in src]
+        if len(src) > len(dst):
+            raise ValueError(f"light_bounds: {len(src)} {kind} ranges exceed {len(dst)}")
+        dst[:len(src)] = src
+    return b
+
+
+def light_bounds_device_buffer(device="cuda") -> torch.Tensor:
+    return torch.zeros(_abi.LIGHT_BOUNDS_DEVICE_BYTES, dtype=torch.uint8, device=device)
+
+
+def upload_light_bounds(bounds, d_bounds, stream=None):
+    """Validates the ranges and writes the device record the bounded kernels read (stream-ordered)."""
+    _check(lib().soc_upload_light_bounds(C.byref(bounds), _ptr(d_bounds), _stream(stream)), "upload_light_bounds")
+
+
+def composition(g, target, albedo, emissive, normal, depth, ssao, shadow, clouds, d_globals=None, stream=None, bounds=None,
+                cull=True, shaded_pairs=None):
+    """CompositionTask. bounds (a device record, upload_light_bounds): bounded lights (soc_composition_bounded), with the
+    per-wave light culling unless cull=False (the same bits either way); shaded_pairs: a device u32 that every wave adds
+    the number of lights it ran to (measuring only)."""
+    if bounds is None:
+        if shaded_pairs is not None:
+            raise ValueError("composition: shaded_pairs needs bounds")
+        _check(lib().soc_composition(_gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal),
+                                     img(depth), img(ssao), img(shadow), img(clouds), _stream(stream)), "composition")
+        return
+    _check(lib().soc_composition_bounded(_gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal),
+                                         img(depth), img(ssao), img(shadow), img(clouds), _ptr(bounds),
+                                         _abi.LIGHTS_CULL if cull else 0, _ptr(shaded_pairs), _stream(stream)),
+           "composition_bounded")
 
 
 def histogram_scratch(device="cuda") -> torch.Tensor:
@@ -341,8 +376,17 @@ def histogram_scratch(device="cuda") -> torch.Tensor:
 
 
 def composition_luminance_histogram(g, target, albedo, emissive, normal, depth, ssao, shadow, clouds, auto_exposure,
-                                    scratch, d_globals=None, stream=None):
-    """Composition + luminance histogram (bins added to auto_exposure's buckets; scratch left zeroed)."""
+                                    scratch, d_globals=None, stream=None, bounds=None, cull=True, shaded_pairs=None):
+    """Composition + luminance histogram (bins added to auto_exposure's buckets; scratch left zeroed).
+    bounds, cull, shaded_pairs: as in composition()."""
+    if bounds is not None:
+        _check(lib().soc_composition_luminance_histogram_bounded(
+            _gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal), img(depth), img(ssao), img(shadow),
+            img(clouds), _ptr(auto_exposure), _ptr(scratch), _ptr(bounds), _abi.LIGHTS_CULL if cull else 0,
+            _ptr(shaded_pairs), _stream(stream)), "composition_luminance_histogram_bounded")
+        return
+    if shaded_pairs is not None:
+        raise ValueError("composition_luminance_histogram: shaded_pairs needs bounds")
     _check(lib().soc_composition_luminance_histogram(
         _gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal), img(depth), img(ssao), img(shadow),
         img(clouds), _ptr(auto_exposure), _ptr(scratch), _stream(stream)), "composition_luminance_histogram")
@@ -556,6 +600,13 @@ class Renderer:
     def set_exposure_pixels(self, total_pixels: int, wide: bool) -> None:
         _check(lib().soc_renderer_set_exposure_pixels(self.handle, int(total_pixels), int(bool(wide))),
                "soc_renderer_set_exposure_pixels")
+
+    def set_light_bounds(self, d_bounds, cull: bool = True) -> None:
+        """Composition with bounded lights on the device record d_bounds (upload_light_bounds; the caller rewrites it
+        between frames on its stream and keeps it alive); None: back to the unbounded lights."""
+        self._light_bounds = d_bounds
+        _check(lib().soc_renderer_set_light_bounds(self.handle, _ptr(d_bounds), _abi.LIGHTS_CULL if cull else 0),
+               "soc_renderer_set_light_bounds")
 
     def pass_names(self):
         n = lib().soc_renderer_pass_count(self.handle)

@@ -204,12 +204,20 @@ MATERIAL_NORMAL_TEXTURE = 4
 MATERIAL_MIPMAPPED = 8
 MATERIAL_PAIRED_TEXELS = 16
 
+class LightBounds(C.Structure):
+    """soc_light_bounds: a range per light, indexed like Globals.point_lights / spot_lights (0: unlimited)."""
+    _fields_ = [("point_range", C.c_float * 128), ("spot_range", C.c_float * 128)]
+
+
+LIGHT_BOUNDS_DEVICE_BYTES = 2048
+LIGHTS_CULL = 1
+
 STRUCTS = {"soc_img": SocImg, "soc_globals": Globals, "soc_sun_info": SunInfo, "soc_point_light": PointLight,
            "soc_spot_light": SpotLight, "soc_auto_exposure": AutoExposure, "soc_camera": Camera,
            "soc_frame_images": FrameImages, "soc_mesh": Mesh, "soc_material": Material,
            "soc_raster_scene": RasterScene, "soc_pass_desc": PassDesc, "soc_entity": Entity,
            "soc_transform": Transform, "soc_draw": Draw, "soc_draw_scene": DrawSceneStruct,
-           "soc_terrain_layer": TerrainLayer}
+           "soc_terrain_layer": TerrainLayer, "soc_light_bounds": LightBounds}
 
 _I = C.c_int
 _P = C.c_void_p
@@ -256,6 +264,11 @@ FUNCTIONS = {
     "soc_copy_image": (_I, [_IMG, _IMG, _P]),
     "soc_tone_mapping": (_I, [_G, _IMG, _P, _IMG, _P]),
     "soc_upload_globals": (_I, [_G, _P, _P]),
+    "soc_upload_light_bounds": (_I, [C.POINTER(LightBounds), _P, _P]),
+    "soc_composition_bounded": (_I, [_G, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _P, C.c_uint32, _P, _P]),
+    "soc_composition_luminance_histogram_bounded": (_I, [_G, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _P, _P, _P,
+                                                         C.c_uint32, _P, _P]),
+    "soc_renderer_set_light_bounds": (_I, [_P, _P, C.c_uint32]),
     "soc_renderer_create": (_P, [C.POINTER(FrameImages), C.c_uint32]),
     "soc_renderer_destroy": (None, [_P]),
     "soc_renderer_execute": (_I, [_P, _G, C.c_int32, _P]),

@@ -165,6 +165,7 @@ const FieldInfo kFields[] = {
     F(soc_entity, color), F(soc_entity, intensity), F(soc_entity, cut_off), F(soc_entity, outer_cut_off),
     F(soc_pass_desc, name), F(soc_pass_desc, group), F(soc_pass_desc, phase), F(soc_pass_desc, flags),
     F(soc_pass_desc, read_count), F(soc_pass_desc, write_count), F(soc_pass_desc, reads), F(soc_pass_desc, writes),
+    F(soc_light_bounds, point_range), F(soc_light_bounds, spot_range),
 };
 #undef F
 struct TypeInfo { const char* type; size_t size; };
@@ -172,7 +173,7 @@ struct TypeInfo { const char* type; size_t size; };
 const TypeInfo kTypes[] = {
     T(soc_img), T(soc_globals), T(soc_sun_info), T(soc_point_light), T(soc_spot_light), T(soc_auto_exposure), T(soc_camera),
     T(soc_frame_images), T(soc_mesh), T(soc_material), T(soc_raster_scene), T(soc_transform), T(soc_draw), T(soc_draw_scene),
-    T(soc_terrain_layer), T(soc_pass_desc), T(soc_entity),
+    T(soc_terrain_layer), T(soc_pass_desc), T(soc_entity), T(soc_light_bounds),
 };
 #undef T
 }  // namespace

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "bloom_w.hpp"
+#include "light_cull.hpp"
 #include "luminance.hpp"
 #include "soc_internal.hpp"
 
@@ -75,6 +76,9 @@ __device__ __forceinline__ float vnan_outside1(float x, float r) { return fabsf(
 __device__ __forceinline__ f2v vnan_outside1(f2v x, f2v r) {
     return f2v{fabsf(x.x) > 1.0f ? __builtin_nanf("") : r.x, fabsf(x.y) > 1.0f ? __builtin_nanf("") : r.y};
 }
+// a where f > 0, else b (a NaN f takes b): the select of the bounded lights, per pixel of the pair
+__device__ __forceinline__ float vsel_pos(float f, float a, float b) { return f > 0.0f ? a : b; }
+__device__ __forceinline__ f2v vsel_pos(f2v f, f2v a, f2v b) { return f2v{f.x > 0.0f ? a.x : b.x, f.y > 0.0f ? a.y : b.y}; }
 __device__ __forceinline__ float vdiv(float a, float b) { return a / b; }
 __device__ __forceinline__ f2v vdiv(f2v a, float b) { return f2v{a.x / b, a.y / b}; }
 template <class T> __device__ __forceinline__ T vdot(const V3<T>& a, const V3<T>& b) {
@@ -122,18 +126,65 @@ __device__ __forceinline__ T spec_exp_acos2(T c) {
 // exp(-acos(x)^2) as one polynomial (spec_exp_acos2). The pixel's view_dir is hoisted out of the loop and the
 // frag_color (albedo) factor out of the sum. Within the RGBA16F tolerance of the oracle's libm restatement.
 // Light records are wave-uniform (scalar loads from the device globals).
-template <class T>
+//
+// Bounded lights (LB & kLbBounded; soc_composition_bounded): a light with a range r > 0 is multiplied by
+// the window w = clamp(1 - (d^2 / r^2)^2, 0, 1), d^2 the dot(l, l) above and 1 / r^2 the upload's rounded reciprocal
+// (LightBoundsDev; 0: unlimited, no window and no extra rounding). With f = w for a point light and f = w * cone term for
+// a spot light (the cone term alone when unlimited), a light is added to a pixel only where f > 0: a select on the
+// accumulator, not a multiply, so a rejected light leaves the pixel's bits untouched whatever its term is (NaN outside a
+// spot's cone for a non-unit normal, Inf at d = 0). An unlimited point light is added as in the unbounded form.
+// LB & kLbCull: every lane of the wave calls (the unlit ones ride along, as a sky pixel's half does), and the loops walk
+// the wave's light masks instead of 0 .. n: mask_of(0 / 1) the point lights 0-63 / 64-127 that may reach a lit pixel of
+// the wave, mask_of(2 / 3) the spot lights (composition_pair's cull; each is asked for just before its loop, so one mask
+// is live at a time). The index stays scalar, so the records still come through the scalar unit. *ran: lights run.
+constexpr int kLbBounded = 1, kLbCull = 2, kLbCount = 4;
+struct NoMasks {
+    __device__ uint64_t operator()(int) const { return 0ull; }
+};
+__device__ __forceinline__ uint64_t uniform64(uint64_t m) {
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(m >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)m);
+}
+// composition_pair's cull: lane i's test of light 64 (which & 1) + i against the box of the wave's lit pixels
+// (light_cull.hpp: a ranged light by its distance to the box, a spot light also by its outer cone against the box's
+// bounding sphere; an unlimited point light always passes), balloted and made provably wave-uniform
+struct CullMasks {
+    light_cull::Aabb box;
+    bool any_lit;   // else every mask is empty
+    uint32_t lane, npl, nsl;
+    const soc_globals* dg;
+    const LightBoundsDev* lb;
+    __device__ __forceinline__ uint64_t operator()(int which) const {
+        const uint32_t i = 64u * (which & 1) + lane;
+        bool keep = false;
+        if (which < 2) {
+            if (any_lit && i < npl) {
+                const float r2 = lb->point_r2[i];
+                keep = !(r2 > 0.0f) || !light_cull::sphere_outside_aabb(box, dg->point_lights[i].position, r2);
+            }
+        } else if (any_lit && i < nsl) {
+            const soc_spot_light& L = dg->spot_lights[i];
+            const float r2 = lb->spot_r2[i];
+            keep = !(r2 > 0.0f && light_cull::sphere_outside_aabb(box, L.position, r2)) &&
+                   !light_cull::cone_outside_aabb(box, L.position, L.direction, L.cut_off, L.outer_cut_off);
+        }
+        return uniform64(__ballot(keep));
+    }
+};
+template <int LB = 0, class T, class MaskOf = NoMasks>
 __device__ __forceinline__ V3<T> light_sum(const soc_globals* __restrict__ dg, uint32_t npl, uint32_t nsl, const V3<T>& n,
-                                           const V3<T>& pos, f3 cam) {
+                                           const V3<T>& pos, f3 cam, const LightBoundsDev* __restrict__ lb = nullptr,
+                                           MaskOf mask_of = {}, uint32_t* ran = nullptr) {
     const T z = pos.x;   // lane-type witness for the broadcasts
     const V3<T> vd0 = {bcv(cam.x, z) - pos.x, bcv(cam.y, z) - pos.y, bcv(cam.z, z) - pos.z};
     const T vk = vrsq(vdot(vd0, vd0));
     const V3<T> view_dir = {vd0.x * vk, vd0.y * vk, vd0.z * vk};
     V3<T> acc = {bcv(0.0f, z), bcv(0.0f, z), bcv(0.0f, z)};
     const T nlog2e = bcv(-1.44269504088896f, z);
+    T d2;   // the last light's squared distance (the bounded forms' window)
     auto shade_light = [&](const float* lp, T& inv, V3<T>& ld) {
         const V3<T> l = {bcv(lp[0], z) - pos.x, bcv(lp[1], z) - pos.y, bcv(lp[2], z) - pos.z};
-        inv = vrsq(vdot(l, l));
+        d2 = vdot(l, l);
+        inv = vrsq(d2);
         ld = V3<T>{l.x * inv, l.y * inv, l.z * inv};
         const V3<T> h = {ld.x + view_dir.x, ld.y + view_dir.y, ld.z + view_dir.z};
         const T c = vdot(h, n) * vrsq(vdot(h, h));
@@ -150,6 +201,60 @@ __device__ __forceinline__ V3<T> light_sum(const soc_globals* __restrict__ dg, u
 #ifndef SOC_COMP_LIGHT_UNROLL
 #define SOC_COMP_LIGHT_UNROLL 2
 #endif
+    if constexpr (LB != 0) {
+        auto add_where = [&](const float* col, T s, T f) {
+            acc = V3<T>{vsel_pos(f, vfma(bcv(col[0], z), s, acc.x), acc.x), vsel_pos(f, vfma(bcv(col[1], z), s, acc.y), acc.y),
+                        vsel_pos(f, vfma(bcv(col[2], z), s, acc.z), acc.z)};
+        };
+        auto window = [&](float inv_r2) {
+            const T q = d2 * bcv(inv_r2, z);
+            return vclamp01(vfma(-q, q, bcv(1.0f, z)));
+        };
+        auto point = [&](uint32_t i) {
+            const soc_point_light& L = dg->point_lights[i];
+            const float inv_r2 = lb->point_inv_r2[i];
+            T inv;
+            V3<T> ld;
+            const T s = shade_light(L.position, inv, ld) * bcv(L.intensity, z);
+            if (inv_r2 == 0.0f) {   // wave-uniform
+                add(L.color, s);
+            } else {
+                const T w = window(inv_r2);
+                add_where(L.color, s * w, w);
+            }
+        };
+        auto spot = [&](uint32_t i) {
+            const soc_spot_light& L = dg->spot_lights[i];
+            const float inv_r2 = lb->spot_inv_r2[i];
+            T inv;
+            V3<T> ld;
+            const T b = shade_light(L.position, inv, ld);
+            const float sdx = -L.direction[0], sdy = -L.direction[1], sdz = -L.direction[2];
+            const float sk = __builtin_amdgcn_rsqf(__builtin_fmaf(sdz, sdz, __builtin_fmaf(sdy, sdy, sdx * sdx)));
+            const T theta = vfma(ld.z, bcv(sdz, z), vfma(ld.y, bcv(sdy, z), ld.x * bcv(sdx, z))) * bcv(sk, z);
+            T f = vclamp01(vdiv(theta - bcv(L.outer_cut_off, z), L.cut_off - L.outer_cut_off));
+            if (inv_r2 != 0.0f) f = window(inv_r2) * f;
+            add_where(L.color, b * bcv(L.intensity, z) * f, f);
+        };
+        if constexpr ((LB & kLbCull) != 0) {
+            uint32_t count = 0u;
+            auto walk = [&](int which, auto&& light) {
+                uint64_t m = mask_of(which);
+                count += (uint32_t)__builtin_popcountll(m);
+#pragma unroll 1
+                for (; m; m &= m - 1) light(64u * (which & 1) + (uint32_t)__builtin_ctzll(m));
+            };
+            walk(0, point);
+            if (npl > 64u) walk(1, point);
+            walk(2, spot);
+            if (nsl > 64u) walk(3, spot);
+            *ran = count;
+        } else {
+            for (uint32_t i = 0; i < npl; ++i) point(i);
+            for (uint32_t i = 0; i < nsl; ++i) spot(i);
+        }
+        return acc;
+    }
 #pragma unroll SOC_COMP_LIGHT_UNROLL
     for (uint32_t i = 0; i < npl; ++i) {            // calculate_point_light, :124-139
         const soc_point_light& L = dg->point_lights[i];
@@ -221,14 +326,14 @@ __device__ __forceinline__ f4 shade_post(const CompParams& p, const ShadePre& s,
     const f3 c = (direct + mk3(p.ambient[0], p.ambient[1], p.ambient[2])) * albedo * s.occl + s.em;
     return f4{c.x, c.y, c.z, 1.0f};
 }
-template <bool LIGHTS = true, typename ShadowImg = DImg>
+template <bool LIGHTS = true, typename ShadowImg = DImg, int LB = 0>
 __device__ __forceinline__ f4 shade(const CompParams& p, float u, float v, float d, f3 albedo, f3 emissive, f3 n,
-                                    float ssao, const ShadowImg& shadow) {
+                                    float ssao, const ShadowImg& shadow, const LightBoundsDev* lb = nullptr) {
     const ShadePre s = shade_pre(p, u, v, d, emissive, n, ssao, shadow);
     if (LIGHTS && (p.npl | p.nsl)) {
         const f3 wp = world_pos(p, u, v, d);
-        const V3<float> ls = light_sum(p.dg, p.npl, p.nsl, V3<float>{n.x, n.y, n.z}, V3<float>{wp.x, wp.y, wp.z},
-                                       mk3(p.cam[0], p.cam[1], p.cam[2]));
+        const V3<float> ls = light_sum<LB>(p.dg, p.npl, p.nsl, V3<float>{n.x, n.y, n.z}, V3<float>{wp.x, wp.y, wp.z},
+                                           mk3(p.cam[0], p.cam[1], p.cam[2]), lb);
         const f3 l3 = f3{ls.x, ls.y, ls.z};
         return shade_post(p, s, albedo, &l3);
     }
@@ -264,10 +369,35 @@ constexpr int BX = 64, BY = 4;
 #ifndef SOC_COMP_LIGHT_WAVES
 #define SOC_COMP_LIGHT_WAVES 6
 #endif
-template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false>
+// LB (0: the kernels as they were, same signature, same instructions: profiles/light_bounds_isa_identity.txt; else the
+// parameter block is CompParamsBounded): the bounded lights of light_sum, in instantiations of their own.
+// kLbCull: before the loops each wave reduces the world-space box of its lit pixels (sky, out-of-image and, in the
+// kernels without the histogram, the lanes that would have left: +-inf), lane i tests lights i and i + 64 of each kind
+// against it (light_cull.hpp: a ranged light by its distance to the box, a spot light also by its outer cone against the
+// box's bounding sphere; an unlimited point light always passes), and the ballots, made provably wave-uniform, are the
+// masks the loops walk. A wave without a lit pixel has empty masks. kLbCount: the wave adds the number of lights its
+// loops run to *la.shaded (the measuring calls only: one same-address atomic per wave).
+struct LightArgs {
+    const LightBoundsDev* lb;
+    uint32_t* shaded;
+};
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+struct CompParamsBounded : CompParams {
+    LightArgs la;
+};
+template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false, int LB = 0>
 __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGHTS && !BL ? SOC_COMP_LIGHT_WAVES : 1))) void composition_pair(DImg target, DImg albedo, DImg emissive, DImg normal, DImg depth,
-                                                        DImg ssao, DImg shadow, DImg clouds, CompParams p, DImg mip1, DImg mip3) {
+                                                        DImg ssao, DImg shadow, DImg clouds, std::conditional_t<LB != 0, CompParamsBounded, CompParams> p, DImg mip1, DImg mip3) {
     static_assert(!SP || ((LIGHTS || BL) && HIST), "SP: the LIGHTS / BL kernels' form of p.bloom_sparse (the render graph's launches)");
+    static_assert(LB == 0 || (LIGHTS && (LB & kLbBounded)), "LB: forms of the lights kernels");
+    static_assert(!(LB & kLbCount) || (!BL && !SP), "the counting forms are the stand-alone calls'");
+    constexpr bool CULL = (LB & kLbCull) != 0;
+    LightArgs la = {};
+    if constexpr (LB != 0) la = p.la;
     static_assert(!BL || HIST, "the in-kernel bloom runs in the fused-histogram kernel (no early exit before its barriers)");
     // a wave covers 16x8 pixels (8 lanes x 2 pixels per row, 8 rows): every row segment is one
     // 128-B line of each G-buffer image, and the wave's shadow-map taps form a compact 2D patch
@@ -292,7 +422,7 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
     // the lights kernels vote at once: the taps held across the G-buffer loads cost them registers they do not have
     bool bloom_zero = false;
     if (LIGHTS && prove) bloom_zero = zero_cells_vote<1, false>(zt);
-    if (!HIST && !inside) return;
+    if (!HIST && !CULL && !inside) return;   // CULL: every lane stays for the wave's reduction (neutral, no access)
     uint2 outp[2] = {uint2{0u, 0u}, uint2{0u, 0u}};
     uint32_t own = 3u;   // bit k: this kernel writes (and bins) pixel k of the pair
     // buffer descriptors + 32-bit offsets (one multiply-add per image row instead of 64-bit pointer math)
@@ -331,14 +461,16 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
             e4 = uint4{b0.x, b0.y, b1.x, b1.y};
         }
     }
-    if (inside) {
+    if (CULL || inside) {
         // LIGHTS: the light sum of the lane's two pixels runs once, as packed pairs (light_sum<f2v>, the same bits per
         // pixel as light_sum<float>); a sky pixel of the pair rides along in the other half and is discarded
         ShadePre pre[2];
         f3 alb[2], nrm[2], wps[2];
+        if constexpr (CULL) nrm[0] = nrm[1] = wps[0] = wps[1] = f3{0.0f, 0.0f, 0.0f};   // a lane outside the image rides along
         uint32_t lit = 0u;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
+            if (CULL && !inside) continue;   // stays unlit and unwritten
             const float u = centre_uv_rn(x + k, target.w, p.rw);
             const float d = k ? d2.y : d2.x;
             const f4 al = unpack_h4(k ? uint2{a4.z, a4.w} : uint2{a4.x, a4.y});
@@ -368,10 +500,34 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
             }
             outp[k] = pack_h4(c);
         }
-        if (LIGHTS && lit) {
+        // CULL, all 64 lanes here: the box of the wave's lit pixels (fminf drops a NaN coordinate: such a pixel fails every
+        // bounded light's own test as well)
+        std::conditional_t<CULL, CullMasks, NoMasks> mask_of = {};
+        if constexpr (CULL) {
+            constexpr float kInf = __builtin_inff();
+            auto lo = [&](float w0, float w1) { return wave_min(fminf((lit & 1u) ? w0 : kInf, (lit & 2u) ? w1 : kInf)); };
+            mask_of.box = light_cull::Aabb{lo(wps[0].x, wps[1].x),     lo(wps[0].y, wps[1].y),     lo(wps[0].z, wps[1].z),
+                                           -lo(-wps[0].x, -wps[1].x), -lo(-wps[0].y, -wps[1].y), -lo(-wps[0].z, -wps[1].z)};
+            mask_of.any_lit = __ballot(lit != 0u) != 0ull;
+            mask_of.lane = (uint32_t)lane;
+            mask_of.npl = p.npl;
+            mask_of.nsl = p.nsl;
+            mask_of.dg = p.dg;
+            mask_of.lb = la.lb;
+        }
+        if constexpr (!CULL && (LB & kLbCount) != 0) {   // the lanes inside the image: the first of them counts
+            const uint64_t here = __ballot(true);
+            if (__ballot(lit != 0u) != 0ull && lane == __builtin_ctzll(here)) atomicAdd(la.shaded, p.npl + p.nsl);
+        }
+        bool sum_lights = lit != 0u;
+        if constexpr (CULL) sum_lights = mask_of.any_lit;   // wave-uniform: all lanes or none
+        if (LIGHTS && sum_lights) {
+            uint32_t ran = 0u;
             const V3<f2v> n2 = {f2v{nrm[0].x, nrm[1].x}, f2v{nrm[0].y, nrm[1].y}, f2v{nrm[0].z, nrm[1].z}};
             const V3<f2v> w2 = {f2v{wps[0].x, wps[1].x}, f2v{wps[0].y, wps[1].y}, f2v{wps[0].z, wps[1].z}};
-            const V3<f2v> ls = light_sum(p.dg, p.npl, p.nsl, n2, w2, mk3(p.cam[0], p.cam[1], p.cam[2]));
+            const V3<f2v> ls = light_sum<LB>(p.dg, p.npl, p.nsl, n2, w2, mk3(p.cam[0], p.cam[1], p.cam[2]), la.lb, mask_of, &ran);
+            if constexpr (CULL && (LB & kLbCount) != 0)
+                if (lane == 0 && ran) atomicAdd(la.shaded, ran);
 #pragma unroll
             for (int k = 0; k < 2; ++k)
                 if (lit & (1u << k)) {
@@ -382,6 +538,7 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
         const uint4 o = uint4{outp[0].x, outp[0].y, outp[1].x, outp[1].y};
         typedef uint32_t v4w __attribute__((ext_vector_type(4)));
         const int to = buf_row(bt, y) + x * 8;
+        if (CULL && !inside) own = 0u;   // nothing to store
         if (own == 3u) {
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4w, o), bt.r, to, 0, (NT & 2) ? 2 : 0);
         } else {   // a sky pixel in the pair belongs to the second lane: 8-B stores of ours only
@@ -402,7 +559,6 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
         if (n) atomicAdd(&p.bins[((blockIdx.y * gridDim.x + blockIdx.x) & 7u) * kBins + threadIdx.x], n);
     }
 }
-
 // The sky pixels of the colour image (composition.inl:220-222: depth == 1 -> color = clouds texel), written and
 // binned on the renderer's second lane right after CloudRendering, so Composition (sky_external) does not wait
 // for the clouds: the same tiling, texel fetch, f16 packing and bins as composition_pair's sky branch, hence
@@ -467,8 +623,10 @@ __global__ __launch_bounds__(kBins) void histogram_fold(uint32_t* __restrict__ s
 }
 
 // Generic path: every input is sampled under the sampling contract.
-__global__ __launch_bounds__(kWorkgroup) void composition_generic(DImg target, DImg albedo, DImg emissive, DImg normal,
-                                                           DImg depth, DImg ssao, DImg shadow, DImg clouds, CompParams p) {
+template <int LB>
+__device__ __forceinline__ void composition_generic_body(const DImg& target, const DImg& albedo, const DImg& emissive, const DImg& normal,
+                                                         const DImg& depth, const DImg& ssao, const DImg& shadow, const DImg& clouds,
+                                                         const CompParams& p, const LightBoundsDev* lb) {
     const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
     if (x >= target.w || y >= target.h) return;
     const float u = centre_uv(x, target.w), v = centre_uv(y, target.h);
@@ -479,10 +637,20 @@ __global__ __launch_bounds__(kWorkgroup) void composition_generic(DImg target, D
         c = f4{cl.x, cl.y, cl.z, 1.0f};
     } else {
         const f4 al = sample_h4(albedo, u, v), em = sample_h4(emissive, u, v), nn = sample_h4(normal, u, v);
-        c = shade(p, u, v, d, f3{al.x, al.y, al.z}, f3{em.x, em.y, em.z}, f3{nn.x, nn.y, nn.z}, sample_r8(ssao, u, v),
-                  shadow);
+        c = shade<true, DImg, LB>(p, u, v, d, f3{al.x, al.y, al.z}, f3{em.x, em.y, em.z}, f3{nn.x, nn.y, nn.z}, sample_r8(ssao, u, v),
+                                  shadow, lb);
     }
     row_ptr_w<uint2>(target, y)[x] = pack_h4(c);
+}
+__global__ __launch_bounds__(kWorkgroup) void composition_generic(DImg target, DImg albedo, DImg emissive, DImg normal,
+                                                           DImg depth, DImg ssao, DImg shadow, DImg clouds, CompParams p) {
+    composition_generic_body<0>(target, albedo, emissive, normal, depth, ssao, shadow, clouds, p, nullptr);
+}
+// bounded lights, every pixel by its own test (no wave patches here: no cull and no count)
+__global__ __launch_bounds__(kWorkgroup) void composition_generic_bounded(DImg target, DImg albedo, DImg emissive, DImg normal,
+                                                           DImg depth, DImg ssao, DImg shadow, DImg clouds, CompParams p,
+                                                           const LightBoundsDev* lb) {
+    composition_generic_body<kLbBounded>(target, albedo, emissive, normal, depth, ssao, shadow, clouds, p, lb);
 }
 
 bool aligned16(const soc_img& im) {
@@ -495,6 +663,20 @@ bool aligned16(const soc_img& im) {
 using namespace soc;
 
 namespace {
+using PairBounded = void (*)(DImg, DImg, DImg, DImg, DImg, DImg, DImg, DImg, CompParamsBounded, DImg, DImg);
+// the bounded form of the lights kernel a launch takes: lb = kLbBounded, with kLbCull and (stand-alone calls) kLbCount
+template <bool HIST, bool BL, bool SP>
+PairBounded pair_bounded(int lb) {
+    if constexpr (!BL && !SP) {
+        if (lb == (kLbBounded | kLbCount)) return composition_pair<HIST, true, 0, BL, SP, kLbBounded | kLbCount>;
+        if (lb == (kLbBounded | kLbCull | kLbCount)) return composition_pair<HIST, true, 0, BL, SP, kLbBounded | kLbCull | kLbCount>;
+    }
+    if (lb == (kLbBounded | kLbCull)) return composition_pair<HIST, true, 0, BL, SP, kLbBounded | kLbCull>;
+    return lb == kLbBounded ? composition_pair<HIST, true, 0, BL, SP, kLbBounded> : nullptr;
+}
+// what a bounded call adds to composition_launch's arguments (null: the unbounded kernels)
+using BoundedCall = soc::LightBoundsCall;
+
 // bins != nullptr: the fused histogram variant if the pair path applies at the globals' resolution
 // (returns 1 otherwise, having launched nothing)
 // bloom_mip1 != nullptr (the render graph under SOC_RENDERER_BLOOM_IN_COMPOSITION): the bloom output is computed in the
@@ -504,7 +686,8 @@ namespace {
 int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo, soc_img emissive,
                        soc_img normal, soc_img depth, soc_img ssao, soc_img shadow, soc_img clouds, uint32_t* bins,
                        uint32_t* scratch, soc_stream stream, bool fold = true, bool sky_external = false,
-                       const soc_img* bloom_mip1 = nullptr, const soc_img* bloom_mip3 = nullptr) {
+                       const soc_img* bloom_mip1 = nullptr, const soc_img* bloom_mip3 = nullptr,
+                       const BoundedCall* bc = nullptr) {
     static const char* P = "soc_composition";
     if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
     int rc = check_img(target, SOC_FMT_RGBA16F, P, "target");
@@ -550,6 +733,8 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
     p.sky_external = 0;
     if ((p.npl || p.nsl) && !d_globals)
         return set_error(SOC_E_INVALID_ARG, "%s: frame has lights but no device globals (soc_upload_globals)", P);
+    if (bc && !bc->d_bounds) return set_error(SOC_E_INVALID_ARG, "%s: bounded call without light bounds (soc_upload_light_bounds)", P);
+    if (bc && (bc->flags & ~(uint32_t)SOC_LIGHTS_CULL)) return set_error(SOC_E_INVALID_ARG, "%s: unknown light flags %u", P, bc->flags);
 
     const int W = target.width, H = target.height;
     auto same = [&](const soc_img& im) { return im.width == W && im.height == H; };
@@ -575,6 +760,24 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
     if (fast) {
         dim3 grd(ceil_div(W, 32), ceil_div(H, 16));
         const bool lights = (p.npl | p.nsl) != 0;
+        // bounded lights: a frame without lights has nothing to bound and takes the kernels below
+        PairBounded kb = nullptr;
+        if (bc && lights) {
+            const int lb = kLbBounded | ((bc->flags & SOC_LIGHTS_CULL) ? kLbCull : 0) | (bc->d_shaded_pairs ? kLbCount : 0);
+            if (!bins) kb = pair_bounded<false, false, false>(lb);
+            else if (bloom_mip1 && bloom_mip3) kb = pair_bounded<true, true, true>(lb);
+            else if (bloom_mip1) kb = pair_bounded<true, true, false>(lb);
+            else if (bloom_mip3) kb = pair_bounded<true, false, true>(lb);
+            else kb = pair_bounded<true, false, false>(lb);
+            if (!kb) return set_error(SOC_E_INVALID_ARG, "%s: the shaded-pairs counter is the stand-alone calls'", P);
+        }
+        auto launch_bounded = [&](const DImg& m1) {
+            CompParamsBounded pb;
+            static_cast<CompParams&>(pb) = p;
+            pb.la = LightArgs{static_cast<const LightBoundsDev*>(bc->d_bounds), bc->d_shaded_pairs};
+            launch("composition_pair", kWorkgroup, kb, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
+                   dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), pb, m1, m3);
+        };
 #define SOC_COMP_PAIR(HI, LI) launch("composition_pair", kWorkgroup, composition_pair<HI, LI>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), \
             dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3)
         if (bins) {
@@ -583,7 +786,9 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
             p.lmin = g->log_min_luminance;
             p.lrange = g->log_max_luminance - g->log_min_luminance;
             p.bf = bin_fast_params(p.lmin, p.lrange);
-            if (bloom_mip1 && lights && bloom_mip3)
+            if (kb)
+                launch_bounded(bloom_mip1 ? dimg(*bloom_mip1) : DImg{});
+            else if (bloom_mip1 && lights && bloom_mip3)
                 launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, true, true>, grd, kWorkgroup, 0, hs(stream),
                        dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
                        dimg(clouds), p, dimg(*bloom_mip1), m3);
@@ -612,6 +817,8 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
                     dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
             else SOC_COMP_PAIR(true, false);
             if (fold) launch("histogram_fold", kBins, histogram_fold, 1, kBins, 0, hs(stream), scratch, bins);
+        } else if (kb) {
+            launch_bounded(DImg{});
         } else if (nt && !lights && aop) {
             launch("composition_pair", kWorkgroup, composition_pair<false, false, 7>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
                 dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
@@ -627,7 +834,11 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
 #undef SOC_COMP_PAIR
     } else {
         dim3 blk(BX, BY), grd(ceil_div(W, BX), ceil_div(H, BY));
-        launch("composition_generic", kWorkgroup, composition_generic, grd, blk, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive), dimg(normal),
+        if (bc && (p.npl | p.nsl))
+            launch("composition_generic_bounded", kWorkgroup, composition_generic_bounded, grd, blk, 0, hs(stream), dimg(target),
+                   dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p,
+                   static_cast<const LightBoundsDev*>(bc->d_bounds));
+        else launch("composition_generic", kWorkgroup, composition_generic, grd, blk, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive), dimg(normal),
                                                          dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p);
     }
     return check_launch("composition");
@@ -676,22 +887,32 @@ extern "C" int soc_composition(const soc_globals* g, const soc_globals* d_global
                               stream);
 }
 
+extern "C" int soc_composition_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                                       soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                                       soc_img clouds, const void* d_bounds, uint32_t flags, uint32_t* d_shaded_pairs,
+                                       soc_stream stream) {
+    const BoundedCall bc = {d_bounds, flags, d_shaded_pairs};
+    return composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
+                              stream, true, false, nullptr, nullptr, &bc);
+}
+
 int soc::composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target,
                                          soc_img albedo, soc_img emissive, soc_img normal, soc_img depth, soc_img ssao,
                                          soc_img shadow, soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch,
                                          bool fold, soc_stream stream, bool sky_external, const soc_img* bloom_mip1,
-                                         const soc_img* bloom_mip3) {
+                                         const soc_img* bloom_mip3, const LightBoundsCall* bounds) {
     if (!g || !ae || !scratch)
         return set_error(SOC_E_INVALID_ARG, "soc_composition_luminance_histogram: null globals / auto exposure / scratch");
+    const BoundedCall* bc = bounds;
     int rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds,
-                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1, bloom_mip3);
+                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1, bloom_mip3, bc);
     if (rc <= 0) return rc;   // launched (or failed validation)
     if (bloom_mip3) return set_error(SOC_E_SHAPE, "composition: the bloom's zero cells need the pair path");
     if (bloom_mip1) return set_error(SOC_E_SHAPE, "composition: the in-kernel bloom needs the pair path");
     if (sky_external) return set_error(SOC_E_INVALID_ARG, "composition: sky_external needs the pair path");
     // not fusable: the two passes back to back (same results)
     rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
-                            stream);
+                            stream, true, false, nullptr, nullptr, bc);
     if (rc) return rc;
     return soc_generate_luminance_histogram(g, target, ae, stream);
 }
@@ -708,4 +929,14 @@ extern "C" int soc_composition_luminance_histogram(const soc_globals* g, const s
                                                    uint32_t* scratch, soc_stream stream) {
     return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
                                            scratch, true, stream);
+}
+
+extern "C" int soc_composition_luminance_histogram_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target,
+                                                           soc_img albedo, soc_img emissive, soc_img normal, soc_img depth,
+                                                           soc_img ssao, soc_img shadow, soc_img clouds, soc_auto_exposure* ae,
+                                                           uint32_t* scratch, const void* d_bounds, uint32_t flags,
+                                                           uint32_t* d_shaded_pairs, soc_stream stream) {
+    const LightBoundsCall bc = {d_bounds, flags, d_shaded_pairs};
+    return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
+                                           scratch, true, stream, false, nullptr, nullptr, &bc);
 }

@@ -5,6 +5,7 @@
 // exactly the roundings the oracle's C performs. It is the only host file that needs the flag.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 
@@ -427,5 +428,45 @@ extern "C" int soc_upload_globals(const soc_globals* g, soc_globals* d_globals, 
     if (!g || !d_globals) return set_error(SOC_E_INVALID_ARG, "soc_upload_globals: null argument");
     hipError_t e = hipMemcpyAsync(d_globals, g, sizeof(soc_globals), hipMemcpyHostToDevice, hs(stream));
     if (e != hipSuccess) return set_error(SOC_E_HIP, "soc_upload_globals: %s", hipGetErrorString(e));
+    return SOC_OK;
+}
+
+// The device record of the light ranges (LightBoundsDev): validated first, converted on the host, one copy.
+extern "C" int soc_upload_light_bounds(const soc_light_bounds* host, void* d_bounds, soc_stream stream) {
+    if (!host || !d_bounds) return set_error(SOC_E_INVALID_ARG, "soc_upload_light_bounds: null argument");
+    LightBoundsDev rec;
+    auto convert = [](const float* range, int n, const char* kind, float* inv_r2, float* r2) {
+        for (int i = 0; i < n; ++i) {
+            const float r = range[i];
+            if (!(r >= 0.0f) || std::isinf(r))
+                return set_error(SOC_E_INVALID_ARG, "soc_upload_light_bounds: %s_range[%d] = %g (0 or a finite range > 0)", kind,
+                                 i, (double)r);
+            if (r == 0.0f) {
+                inv_r2[i] = r2[i] = 0.0f;
+                continue;
+            }
+            // r * r over fp32: unlimited to every fp32 distance; under it: the smallest normal square
+            float q = r * r;
+            if (std::isinf(q)) {
+                inv_r2[i] = r2[i] = 0.0f;
+                continue;
+            }
+            if (q < FLT_MIN) q = FLT_MIN;
+            const float inv = 1.0f / q;
+            if (inv < FLT_MIN) {   // the window would be 1 to within fp32 everywhere a distance is finite
+                inv_r2[i] = r2[i] = 0.0f;
+                continue;
+            }
+            inv_r2[i] = inv;
+            r2[i] = q;
+        }
+        return (int)SOC_OK;
+    };
+    int rc = convert(host->point_range, SOC_MAX_POINT_LIGHTS, "point", rec.point_inv_r2, rec.point_r2);
+    if (!rc) rc = convert(host->spot_range, SOC_MAX_SPOT_LIGHTS, "spot", rec.spot_inv_r2, rec.spot_r2);
+    if (rc) return rc;
+    // pageable source: the copy is staged before hipMemcpyAsync returns, so `rec` may leave scope
+    hipError_t e = hipMemcpyAsync(d_bounds, &rec, sizeof rec, hipMemcpyHostToDevice, hs(stream));
+    if (e != hipSuccess) return set_error(SOC_E_HIP, "soc_upload_light_bounds: %s", hipGetErrorString(e));
     return SOC_OK;
 }

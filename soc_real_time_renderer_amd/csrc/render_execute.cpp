@@ -670,6 +670,14 @@ extern "C" int soc_renderer_set_exposure_pixels(soc_renderer* r, uint64_t total_
     return SOC_OK;
 }
 
+extern "C" int soc_renderer_set_light_bounds(soc_renderer* r, const void* d_bounds, uint32_t flags) {
+    if (!r) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_light_bounds: null renderer");
+    if (flags & ~(uint32_t)SOC_LIGHTS_CULL) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_light_bounds: unknown flags %u", flags);
+    r->light_bounds = d_bounds;
+    r->light_flags = d_bounds ? flags : 0u;
+    return SOC_OK;
+}
+
 extern "C" int32_t soc_renderer_current_history(const soc_renderer* r) { return r ? r->hist : -1; }
 
 // Resume from a checkpoint (SURVEY.md §5 "Checkpoint / resume"): the slot whose history_color / history_velocity hold

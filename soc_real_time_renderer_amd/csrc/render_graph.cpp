@@ -249,12 +249,14 @@ void build_passes_tail(soc_renderer* r) {
         add_pass(r, "Composition+GenerateLuminanceHistogram", "Composition", pre, comp_reads,
                  res_mask({SOC_RES_COLOR, SOC_RES_HISTOGRAM_PARTIALS}), [r](const soc_globals* g, hipStream_t s) {
                      const auto& I = r->img;
+                     const soc::LightBoundsCall lb = {r->light_bounds, r->light_flags, nullptr};
                      return soc::composition_luminance_histogram(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
                                                                  I.ssao_blur, I.shadow, I.clouds, I.auto_exposure,
                                                                  r->hist_scratch, false, (soc_stream)s,
                                                                  r->sky_split_active,
                                                                  bloom_in_comp_active(r) ? &I.bloom_mips[1] : nullptr,
-                                                                 r->bloom_cells_frame ? &I.bloom_mips[3] : nullptr);
+                                                                 r->bloom_cells_frame ? &I.bloom_mips[3] : nullptr,
+                                                                 r->light_bounds ? &lb : nullptr);
                  });
         // the 8 partial histograms of the fused launch into the AutoExposure bins. Before a multi-GPU exchange
         // (PRE and POST in separate calls) the fold must precede it; in a one-call frame the resolve folds them
@@ -270,6 +272,10 @@ void build_passes_tail(soc_renderer* r) {
         add_pass(r, "Composition", "Composition", pre, comp_reads, res_mask({SOC_RES_COLOR}),
                  [r](const soc_globals* g, hipStream_t s) {
                      const auto& I = r->img;
+                     if (r->light_bounds)
+                         return soc_composition_bounded(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
+                                                        I.ssao_blur, I.shadow, I.clouds, r->light_bounds, r->light_flags, nullptr,
+                                                        (soc_stream)s);
                      return soc_composition(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth, I.ssao_blur,
                                             I.shadow, I.clouds, (soc_stream)s);
                  });

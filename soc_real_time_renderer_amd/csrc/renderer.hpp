@@ -99,6 +99,9 @@ struct soc_renderer {
     int hist = 0;               // history slot read as "previous" this frame
     uint64_t total_pixels = 0;  // 0 = this frame
     int wide = 0;
+    // soc_renderer_set_light_bounds: Composition launches the bounded kernels on this device record (null: unbounded)
+    const void* light_bounds = nullptr;
+    uint32_t light_flags = 0;
     // pinned staging ring for the device globals upload (lights)
     soc_globals* staging = nullptr;
     hipEvent_t staging_ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -95,13 +95,28 @@ int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const so
                           bool sparse_output = false);
 bool bloom_sparse_applicable();
 
+// The device record of a frame's light ranges (soc_upload_light_bounds writes it, composition.hip reads it; the library's
+// own layout, SOC_LIGHT_BOUNDS_DEVICE_BYTES): per light RN(1 / RN(r * r)) for the window (0: unlimited) and RN(r * r) for
+// the cull (0: unlimited). A range whose square's reciprocal leaves fp32 is stored as the nearest finite / normal value.
+struct LightBoundsDev {
+    float point_inv_r2[SOC_MAX_POINT_LIGHTS], spot_inv_r2[SOC_MAX_SPOT_LIGHTS];
+    float point_r2[SOC_MAX_POINT_LIGHTS], spot_r2[SOC_MAX_SPOT_LIGHTS];
+};
+static_assert(sizeof(LightBoundsDev) == SOC_LIGHT_BOUNDS_DEVICE_BYTES, "soc_rt.h states the device record's size");
+// A bounded Composition launch: the record, SOC_LIGHTS_* flags and the optional per-wave counter of lights run.
+struct LightBoundsCall {
+    const void* d_bounds;
+    uint32_t flags;
+    uint32_t* d_shaded_pairs;
+};
+
 // soc_composition_luminance_histogram with the fold of the 8 partial histograms optionally left to a
 // separate histogram_fold_launch (the render graph times the fold as a pass of its own).
 int composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
                                     soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
                                     soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch, bool fold, soc_stream stream,
                                     bool sky_external = false, const soc_img* bloom_mip1 = nullptr,
-                                    const soc_img* bloom_mip3 = nullptr);
+                                    const soc_img* bloom_mip3 = nullptr, const LightBoundsCall* bounds = nullptr);
 // The fused pair path applies to these images at the globals' resolution (composition.hip).
 bool composition_pair_applicable(const soc_globals* g, const soc_img& target, const soc_img& albedo,
                                  const soc_img& emissive, const soc_img& normal, const soc_img& depth,
