@@ -443,6 +443,55 @@ int soc_composition_luminance_histogram_bounded(const soc_globals* g, const soc_
                                                 const void* d_bounds, uint32_t flags, uint32_t* d_shaded_pairs,
                                                 soc_stream stream);
 
+/* --- Cascaded sun shadow maps (opt-in) ---------------------------------------------
+ * The reference has one fixed orthographic ESM map (sun_info.projection_view_matrix). A caller may instead give
+ * Composition up to four maps fitted to slices of the camera's frustum, stacked vertically in ONE D32F atlas: cascade k
+ * is rows [k * map_size, (k + 1) * map_size) of a map_size x (count * map_size) image.
+ * A lit pixel uses cascade k = the number of i < count - 1 with depth > split_depth[i], compared on the stored float32
+ * depth (a NaN depth: cascade 0; a pixel beyond the last split still samples the last cascade, clamped). The shadow term
+ * is the reference's per cascade: project with projection_view[k], one bilinear tap at xy * 0.5 + 0.5 inside slab k
+ * (clamp-to-edge never reads a neighbouring slab), then clamp(pow(exp(exponential_factor[k] * (z - d)),
+ * sun_info.darkening_factor), 0, 1). No blending between cascades.
+ * The fitted cascades keep the sun's softness in world units, so their factors are large (-1000 .. -2500 for slices
+ * 50 - 200 units wide); the cascaded kernels therefore compute a pixel's sun-space position and tap coordinate in fp64
+ * (from the same fp32 matrices, depth and pixel centre), which soc_composition's fp32 arithmetic cannot hold to the
+ * RGBA16F tolerance at such factors. */
+#define SOC_MAX_SUN_CASCADES 4
+typedef struct soc_sun_cascades {
+    int32_t count;                  /* 1..4 */
+    int32_t map_size;               /* S: cascade k is rows [k*S, (k+1)*S) of an S x (count*S) D32F atlas */
+    float projection_view[4][16];   /* column-major, as sun_info.projection_view_matrix */
+    float split_depth[4];           /* depth-buffer values, strictly increasing; [count-1..] unused */
+    float exponential_factor[4];    /* ESM factor per cascade */
+} soc_sun_cascades;
+/* The one-cascade record of the globals' own sun: projection_matrix * view_matrix in host fp32 and the sun's factor. A
+ * cascaded call with it and the S x S map computes soc_composition's term with the fp64 position: the same bits wherever
+ * the two roundings of the term agree (all of them on the test frames; 94 of 8.3 M pixels differ by one RGBA16F step at
+ * 3840x2160 on the C4 terrain), not by construction. No HIP call. */
+int soc_sun_cascades_from_sun(const soc_globals* g, int32_t map_size, soc_sun_cascades* out);
+/* Fits `count` cascades to the camera's unjittered frustum between near_distance and max_distance (view distances).
+ * Slice far distances: d_i = lambda n (f/n)^(i/N) + (1 - lambda)(n + (f - n) i/N); split_depth[i] is the depth-buffer
+ * value of a view-axis point at d_(i+1). Per slice: the bounding sphere of its eight corners, radius rounded up to a
+ * multiple of 1/8 world unit (the extent does not change when the camera only rotates), centre snapped to whole shadow
+ * texels (2r / map_size) in light space, lookAt along sun_info.direction with up (0, -1, 0), an orthographic projection
+ * whose depth range holds the sphere and anything up to caster_margin world units towards the sun in z_ndc [0, 1].
+ * exponential_factor[k] = sun_info.exponential_factor * P_sun[10] / P_k[10]: the sun's softness in world units.
+ * SOC_E_INVALID_ARG (naming the argument) for count outside 1..4, map_size < 2, split_lambda outside [0, 1], not
+ * 0 < near_distance < max_distance, a negative margin or a non-finite value. No HIP call. */
+int soc_sun_cascades_fit(const soc_globals* g, int32_t count, int32_t map_size, float near_distance, float max_distance,
+                         float split_lambda, float caster_margin, soc_sun_cascades* out);
+/* soc_composition / soc_composition_luminance_histogram with `shadow` = the cascades' atlas. The record is host memory,
+ * consumed before the call returns. Validated before any HIP call (SOC_E_INVALID_ARG naming the field: count, map_size,
+ * the atlas extent or format, split_depth, exponential_factor, projection_view). */
+int soc_composition_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                             soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                             soc_img clouds, const soc_sun_cascades* cascades, soc_stream stream);
+int soc_composition_luminance_histogram_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target,
+                                                 soc_img albedo, soc_img emissive, soc_img normal, soc_img depth,
+                                                 soc_img ssao, soc_img shadow, soc_img clouds,
+                                                 soc_auto_exposure* d_auto_exposure, uint32_t* scratch,
+                                                 const soc_sun_cascades* cascades, soc_stream stream);
+
 /* --- Render graph (host C++ mirror of Renderer::rebuild_task_graph, renderer.cpp:929-1235) ------ */
 
 /* Frame images. The caller allocates them (device memory) and keeps them alive. */
@@ -538,6 +587,12 @@ int soc_renderer_set_exposure_pixels(soc_renderer* r, uint64_t total_pixels, int
  * between frames on its stream (soc_upload_light_bounds), like every frame input; flags: SOC_LIGHTS_*. NULL removes
  * the setting. The pass's declared uses, the graph and the frame plan are unchanged. */
 int soc_renderer_set_light_bounds(soc_renderer* r, const void* d_bounds, uint32_t flags);
+/* Cascaded sun shadows (above): the record is copied (no HIP call; a caller refits and sets it every frame the camera
+ * moves) and images.shadow must be its atlas (checked here and again at execute). While set, SunShadowDraw and
+ * SunShadowDrawTerrain draw every cascade into its slab within their pass (names, lanes and the frame plan unchanged)
+ * and Composition launches the cascaded call. NULL: back to the one map. Together with soc_renderer_set_light_bounds,
+ * SOC_RENDERER_BLOOM_IN_COMPOSITION or the bloom's zero cells: SOC_E_UNSUPPORTED naming the pair. */
+int soc_renderer_set_sun_cascades(soc_renderer* r, const soc_sun_cascades* cascades);
 int32_t soc_renderer_pass_count(const soc_renderer* r);
 const char* soc_renderer_pass_name(const soc_renderer* r, int32_t index);
 const char* soc_renderer_pass_group(const soc_renderer* r, int32_t index);   /* renderer.cpp:558-588 names */

@@ -31,6 +31,7 @@ __all__ = ["SocError", "lib", "img", "Globals", "Camera", "AutoExposure", "globa
            "depth_of_field", "cloud_rendering", "composition", "generate_luminance_histogram",
            "resolve_luminance_histogram", "temporal_antialiasing", "copy_image", "tone_mapping", "upload_globals",
            "light_bounds", "light_bounds_device_buffer", "upload_light_bounds",
+           "sun_cascades_from_sun", "sun_cascades_fit", "sun_cascade_atlas",
            "Renderer", "read_image", "write_png", "write_exr", "FMT_RGBA16F", "FMT_D32F", "FMT_R8_UNORM", "FMT_RGBA8_UNORM", "FMT_RGBA8_SRGB",
            "FMT_RGBA32F", "PHASE_PRE_EXPOSURE", "PHASE_POST_EXPOSURE", "PHASE_ALL"]
 
@@ -353,11 +354,42 @@ def upload_light_bounds(bounds, d_bounds, stream=None):
     _check(lib().soc_upload_light_bounds(C.byref(bounds), _ptr(d_bounds), _stream(stream)), "upload_light_bounds")
 
 
+def sun_cascades_from_sun(g, map_size: int) -> "_abi.SunCascades":
+    """The one-cascade soc_sun_cascades record of the globals' own sun (a cascaded call with it computes composition()'s
+    sun term, with the position in fp64)."""
+    rec = _abi.SunCascades()
+    _check(lib().soc_sun_cascades_from_sun(_gp(g), int(map_size), C.byref(rec)), "sun_cascades_from_sun")
+    return rec
+
+
+def sun_cascades_fit(g, count: int, map_size: int, near: float, max_distance: float, split_lambda: float = 0.5,
+                     caster_margin: float = 64.0) -> "_abi.SunCascades":
+    """soc_sun_cascades_fit: `count` sun shadow maps fitted to the camera's frustum between the view distances `near` and
+    `max_distance`; caster_margin: how far towards the sun (world units) a caster outside a slice may stand."""
+    rec = _abi.SunCascades()
+    _check(lib().soc_sun_cascades_fit(_gp(g), int(count), int(map_size), float(near), float(max_distance),
+                                      float(split_lambda), float(caster_margin), C.byref(rec)), "sun_cascades_fit")
+    return rec
+
+
+def sun_cascade_atlas(record, device="cuda") -> torch.Tensor:
+    """The record's D32F atlas (count * map_size rows of map_size texels), filled with 1.0 (nothing drawn)."""
+    return torch.ones((record.count * record.map_size, record.map_size), dtype=torch.float32, device=device)
+
+
 def composition(g, target, albedo, emissive, normal, depth, ssao, shadow, clouds, d_globals=None, stream=None, bounds=None,
-                cull=True, shaded_pairs=None):
+                cull=True, shaded_pairs=None, cascades=None):
     """CompositionTask. bounds (a device record, upload_light_bounds): bounded lights (soc_composition_bounded), with the
     per-wave light culling unless cull=False (the same bits either way); shaded_pairs: a device u32 that every wave adds
-    the number of lights it ran to (measuring only)."""
+    the number of lights it ran to (measuring only). cascades (a soc_sun_cascades record): `shadow` is its atlas
+    (soc_composition_cascaded); not together with bounds."""
+    if cascades is not None:
+        if bounds is not None or shaded_pairs is not None:
+            raise ValueError("composition: cascades do not combine with bounds")
+        _check(lib().soc_composition_cascaded(_gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal),
+                                              img(depth), img(ssao), img(shadow), img(clouds), C.byref(cascades),
+                                              _stream(stream)), "composition_cascaded")
+        return
     if bounds is None:
         if shaded_pairs is not None:
             raise ValueError("composition: shaded_pairs needs bounds")
@@ -376,9 +408,18 @@ def histogram_scratch(device="cuda") -> torch.Tensor:
 
 
 def composition_luminance_histogram(g, target, albedo, emissive, normal, depth, ssao, shadow, clouds, auto_exposure,
-                                    scratch, d_globals=None, stream=None, bounds=None, cull=True, shaded_pairs=None):
+                                    scratch, d_globals=None, stream=None, bounds=None, cull=True, shaded_pairs=None,
+                                    cascades=None):
     """Composition + luminance histogram (bins added to auto_exposure's buckets; scratch left zeroed).
-    bounds, cull, shaded_pairs: as in composition()."""
+    bounds, cull, shaded_pairs, cascades: as in composition()."""
+    if cascades is not None:
+        if bounds is not None or shaded_pairs is not None:
+            raise ValueError("composition_luminance_histogram: cascades do not combine with bounds")
+        _check(lib().soc_composition_luminance_histogram_cascaded(
+            _gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal), img(depth), img(ssao), img(shadow),
+            img(clouds), _ptr(auto_exposure), _ptr(scratch), C.byref(cascades), _stream(stream)),
+            "composition_luminance_histogram_cascaded")
+        return
     if bounds is not None:
         _check(lib().soc_composition_luminance_histogram_bounded(
             _gp(g), _ptr(d_globals), img(target), img(albedo), img(emissive), img(normal), img(depth), img(ssao), img(shadow),
@@ -607,6 +648,12 @@ class Renderer:
         self._light_bounds = d_bounds
         _check(lib().soc_renderer_set_light_bounds(self.handle, _ptr(d_bounds), _abi.LIGHTS_CULL if cull else 0),
                "soc_renderer_set_light_bounds")
+
+    def set_sun_cascades(self, record) -> None:
+        """Cascaded sun shadows: the record is copied (refit and set it whenever the camera moves); the renderer's shadow
+        image must be the record's atlas (sun_cascade_atlas). None: back to the one map."""
+        _check(lib().soc_renderer_set_sun_cascades(self.handle, None if record is None else C.byref(record)),
+               "soc_renderer_set_sun_cascades")
 
     def pass_names(self):
         n = lib().soc_renderer_pass_count(self.handle)

@@ -211,13 +211,22 @@ class LightBounds(C.Structure):
 
 LIGHT_BOUNDS_DEVICE_BYTES = 2048
 LIGHTS_CULL = 1
+MAX_SUN_CASCADES = 4
+
+
+class SunCascades(C.Structure):
+    """soc_sun_cascades: up to four sun shadow maps stacked in one map_size x count * map_size D32F atlas."""
+    _fields_ = [("count", C.c_int32), ("map_size", C.c_int32), ("projection_view", (C.c_float * 16) * 4),
+                ("split_depth", C.c_float * 4), ("exponential_factor", C.c_float * 4)]
+
 
 STRUCTS = {"soc_img": SocImg, "soc_globals": Globals, "soc_sun_info": SunInfo, "soc_point_light": PointLight,
            "soc_spot_light": SpotLight, "soc_auto_exposure": AutoExposure, "soc_camera": Camera,
            "soc_frame_images": FrameImages, "soc_mesh": Mesh, "soc_material": Material,
            "soc_raster_scene": RasterScene, "soc_pass_desc": PassDesc, "soc_entity": Entity,
            "soc_transform": Transform, "soc_draw": Draw, "soc_draw_scene": DrawSceneStruct,
-           "soc_terrain_layer": TerrainLayer, "soc_light_bounds": LightBounds}
+           "soc_terrain_layer": TerrainLayer, "soc_light_bounds": LightBounds,
+           "soc_sun_cascades": SunCascades}
 
 _I = C.c_int
 _P = C.c_void_p
@@ -269,6 +278,12 @@ FUNCTIONS = {
     "soc_composition_luminance_histogram_bounded": (_I, [_G, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _P, _P, _P,
                                                          C.c_uint32, _P, _P]),
     "soc_renderer_set_light_bounds": (_I, [_P, _P, C.c_uint32]),
+    "soc_sun_cascades_from_sun": (_I, [_G, C.c_int32, C.POINTER(SunCascades)]),
+    "soc_sun_cascades_fit": (_I, [_G, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(SunCascades)]),
+    "soc_composition_cascaded": (_I, [_G, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, C.POINTER(SunCascades), _P]),
+    "soc_composition_luminance_histogram_cascaded": (_I, [_G, _P, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _IMG, _P, _P,
+                                                          C.POINTER(SunCascades), _P]),
+    "soc_renderer_set_sun_cascades": (_I, [_P, C.POINTER(SunCascades)]),
     "soc_renderer_create": (_P, [C.POINTER(FrameImages), C.c_uint32]),
     "soc_renderer_destroy": (None, [_P]),
     "soc_renderer_execute": (_I, [_P, _G, C.c_int32, _P]),

@@ -166,6 +166,8 @@ const FieldInfo kFields[] = {
     F(soc_pass_desc, name), F(soc_pass_desc, group), F(soc_pass_desc, phase), F(soc_pass_desc, flags),
     F(soc_pass_desc, read_count), F(soc_pass_desc, write_count), F(soc_pass_desc, reads), F(soc_pass_desc, writes),
     F(soc_light_bounds, point_range), F(soc_light_bounds, spot_range),
+    F(soc_sun_cascades, count), F(soc_sun_cascades, map_size), F(soc_sun_cascades, projection_view),
+    F(soc_sun_cascades, split_depth), F(soc_sun_cascades, exponential_factor),
 };
 #undef F
 struct TypeInfo { const char* type; size_t size; };
@@ -173,7 +175,7 @@ struct TypeInfo { const char* type; size_t size; };
 const TypeInfo kTypes[] = {
     T(soc_img), T(soc_globals), T(soc_sun_info), T(soc_point_light), T(soc_spot_light), T(soc_auto_exposure), T(soc_camera),
     T(soc_frame_images), T(soc_mesh), T(soc_material), T(soc_raster_scene), T(soc_transform), T(soc_draw), T(soc_draw_scene),
-    T(soc_terrain_layer), T(soc_pass_desc), T(soc_entity), T(soc_light_bounds),
+    T(soc_terrain_layer), T(soc_pass_desc), T(soc_entity), T(soc_light_bounds), T(soc_sun_cascades),
 };
 #undef T
 }  // namespace

@@ -389,11 +389,135 @@ __device__ __forceinline__ float wave_min(float v) {
 struct CompParamsBounded : CompParams {
     LightArgs la;
 };
-template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false, int LB = 0>
+// Cascaded sun shadows (CS; soc_composition_cascaded), in instantiations of their own with a parameter
+// block of their own: `shadow` is the atlas (S x count * S, cascade c = rows [c * S, (c + 1) * S)), pv[c] the cascade's
+// projection_view (world -> sun clip space), ef[c] its ESM factor, split[] the stored depths that separate the cascades
+// (+inf from count - 1 on, so the compares need no count).
+//
+// The pixel's sun-space position and its tap position are computed in fp64, from the same fp32 matrix entries, depth and
+// pixel centre the fp32 kernels use. The fitted cascades keep the sun's softness in WORLD units, so ef[c] grows with the
+// cascade's depth range (-1000 .. -2500 for slices 50 - 200 units wide, against the sun's -80), and the exponent
+// ef * (z - d) magnifies what fp32 leaves of a position 100 units away:
+//  - shade_pre's combined matrix (sun_pv * inv_view * inv_proj in host fp32) has entries of magnitude 5 (inv_proj's w row
+//    is about -5 d + 5) whose sum is 1 / distance: exponent errors of 0.01 - 0.1 on the test frames, 2 - 20 times the
+//    RGBA16F tolerance (fp32 on the CPU against the float64 oracle);
+//  - through the world position with w = fma(m11, d, m15) the exponent holds to 2e-4, but the tap's 8-bit sub-texel
+//    weight (floor(t * 256 + 0.5), the sampling contract) then still rounds the other way than the oracle's on about one
+//    pixel in a thousand (fp32 leaves 1e-3 of a weight step at t = 128 texels), and one weight step between texels a
+//    world unit apart in depth is 0.02 in the exponent: single pixels 1.2 and 2.2 tolerances off in two of six frames.
+// In fp64 both vanish (the position agrees with the oracle's to 1e-12 of a weight step). The price is about 45 fp64 fmas
+// and two divisions per lit pixel (DESIGN.md §5.8 has the timings); the G-buffer, the AO tap and the lights stay fp32.
+struct Mat4d { double m[16]; };
+struct CompParamsCascaded : CompParams {
+    Mat4d inv_proj_d, inv_view_d;          // the globals' fp32 entries, widened
+    Mat4d pv[SOC_MAX_SUN_CASCADES];
+    double rw_d, rh_d;                     // 1 / target width, 1 / target height
+    float split[SOC_MAX_SUN_CASCADES - 1];
+    float ef[SOC_MAX_SUN_CASCADES];
+    int count, S;
+};
+struct d3 { double x, y, z; };
+// the cascade of a stored depth: the number of splits below it (a NaN depth compares false: cascade 0)
+__device__ __forceinline__ int cascade_of(const CompParamsCascaded& p, float d) {
+    return (d > p.split[0] ? 1 : 0) + (d > p.split[1] ? 1 : 0) + (d > p.split[2] ? 1 : 0);
+}
+// M * (x, y, z, 1) -> xyz, w
+__device__ __forceinline__ d3 mul_point(const Mat4d& M, double x, double y, double z, double& w) {
+    const double* m = M.m;
+    w = __builtin_fma(m[3], x, __builtin_fma(m[7], y, __builtin_fma(m[11], z, m[15])));
+    return d3{__builtin_fma(m[0], x, __builtin_fma(m[4], y, __builtin_fma(m[8], z, m[12]))),
+              __builtin_fma(m[1], x, __builtin_fma(m[5], y, __builtin_fma(m[9], z, m[13]))),
+              __builtin_fma(m[2], x, __builtin_fma(m[6], y, __builtin_fma(m[10], z, m[14])))};
+}
+// get_world_position_from_depth (:114-122) of pixel (x, y) with stored depth d, for the cascades' shadow lookup
+__device__ __forceinline__ d3 world_d(const CompParamsCascaded& p, int x, int y, float d) {
+    const double u = ((double)x + 0.5) * p.rw_d, v = ((double)y + 0.5) * p.rh_d;
+    double vw, ww;
+    const d3 vs = mul_point(p.inv_proj_d, __builtin_fma(u, 2.0, -1.0), __builtin_fma(v, 2.0, -1.0), (double)d, vw);
+    const double r = 1.0 / vw;
+    return mul_point(p.inv_view_d, vs.x * r, vs.y * r, vs.z * r, ww);
+}
+// axis_clamp (soc_device.hpp) on a coordinate held in fp64: the same taps and 8-bit weight
+__device__ __forceinline__ Axis axis_clamp_d(double u, int n) {
+    double t = u * (double)n - 0.5;
+    t = fmin(fmax(t, -2.0), (double)n + 1.0);
+    const int fx = (int)floor(t * 256.0 + 0.5);
+    int i = fx >> 8;
+    float w = (float)(fx & 255) * (1.0f / 256.0f);
+    if (i < 0) { i = 0; w = 0.0f; }
+    else if (i >= n - 1) { i = n - 2; w = 1.0f; }
+    Axis a;
+    a.i0 = i;
+    a.i1 = i + 1;   // n >= 2 (validated)
+    a.w = w;
+    return a;
+}
+// sample_f32 on the S x S slab whose first row is row0: the taps and weights of the slab alone (clamp-to-edge stays
+// inside it), the rows then offset
+__device__ __forceinline__ float sample_f32_slab(const BufImg& b, double u, double v, int S, int row0) {
+    typedef float f2u4 __attribute__((ext_vector_type(2))) __attribute__((aligned(4)));
+    const Axis ax = axis_clamp_d(u, S), ay = axis_clamp_d(v, S);
+    const int o = ax.i0 * 4;
+    const f2u4 r0 = __builtin_bit_cast(f2u4, __builtin_amdgcn_raw_buffer_load_b64(b.r, buf_row(b, row0 + ay.i0) + o, 0, 0));
+    const f2u4 r1 = __builtin_bit_cast(f2u4, __builtin_amdgcn_raw_buffer_load_b64(b.r, buf_row(b, row0 + ay.i1) + o, 0, 0));
+    return bilerp1(r0.x, r0.y, r1.x, r1.y, ax.w, ay.w);
+}
+__device__ __forceinline__ float sample_f32_slab(const DImg& im, double u, double v, int S, int row0) {
+    const Axis ax = axis_clamp_d(u, S), ay = axis_clamp_d(v, S);
+    const soc_f2a4 p0 = *reinterpret_cast<const soc_f2a4*>(row_ptr<float>(im, row0 + ay.i0) + ax.i0);
+    const soc_f2a4 p1 = *reinterpret_cast<const soc_f2a4*>(row_ptr<float>(im, row0 + ay.i1) + ax.i0);
+    return bilerp1(p0.x, p0.y, p1.x, p1.y, ax.w, ay.w);
+}
+// The sun ESM shadow (:166-173) of the world position w in cascade c (wave-uniform: the matrix comes through the scalar
+// unit): project, one tap inside slab c, the exponential with the cascade's factor in fp32 as shade_pre has it.
+template <typename ShadowImg>
+__device__ __forceinline__ float cascade_shadow(const CompParamsCascaded& p, int c, const d3& w, const ShadowImg& shadow) {
+    double sw;
+    const d3 sp = mul_point(p.pv[c], w.x, w.y, w.z, sw);
+    const double r = 1.0 / sw;
+    const float pcz = (float)(sp.z * r);
+    const float sd = sample_f32_slab(shadow, __builtin_fma(sp.x * r, 0.5, 0.5), __builtin_fma(sp.y * r, 0.5, 0.5), p.S, c * p.S);
+    float e = __expf(p.ef[c] * (pcz - sd));
+    if (p.df != 1.0f) e = fast_pow(e, p.df);   // pow(x, 1.0) == x exactly
+    return clampf(e, 0.0f, 1.0f);
+}
+// shade_pre without the shadow: direct = dot(n, -sun), to be multiplied by cascade_shadow
+__device__ __forceinline__ ShadePre shade_pre_unshadowed(const CompParams& p, f3 emissive, f3 n, float ssao) {
+    ShadePre s;
+    s.em = emissive * p.emissive_strength;
+    s.occl = fast_pow(ssao, p.ao_strength);
+    s.direct = fmaxf(0.0f, dot3(n, -mk3(p.sun_dir[0], p.sun_dir[1], p.sun_dir[2])));
+    return s;
+}
+// The sun shadows of up to NPX pixels of a lane, each with its own cascade ck[i] (live[i]: the pixel is lit) and world
+// position. The wave walks the cascades: one that no live pixel of the wave selects is skipped (wave-uniform branch),
+// the others run cascade_shadow under the mask of the lanes that selected them. A wave whose pixels share one cascade
+// (the common case on 16 x 8 patches) runs one round; a mixed wave one round per cascade present. A pixel's arithmetic
+// is the same in either case and involves no other lane's values, so its bits do not depend on the wave it is in.
+template <int NPX, typename ShadowImg>
+__device__ __forceinline__ void cascade_shadows(const CompParamsCascaded& p, const bool* live, const int* ck, const d3* w,
+                                                const ShadowImg& shadow, float* out) {
+#pragma unroll 1
+    for (int c = 0; c < p.count; ++c) {
+        bool mine[NPX], any = false;
+#pragma unroll
+        for (int i = 0; i < NPX; ++i) {
+            mine[i] = live[i] && ck[i] == c;
+            any = any || mine[i];
+        }
+        if (__ballot(any) == 0ull) continue;
+#pragma unroll
+        for (int i = 0; i < NPX; ++i)
+            if (mine[i]) out[i] = cascade_shadow(p, c, w[i], shadow);
+    }
+}
+template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false, int LB = 0, bool CS = false>
 __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGHTS && !BL ? SOC_COMP_LIGHT_WAVES : 1))) void composition_pair(DImg target, DImg albedo, DImg emissive, DImg normal, DImg depth,
-                                                        DImg ssao, DImg shadow, DImg clouds, std::conditional_t<LB != 0, CompParamsBounded, CompParams> p, DImg mip1, DImg mip3) {
+                                                        DImg ssao, DImg shadow, DImg clouds,
+                                                        std::conditional_t<CS, CompParamsCascaded, std::conditional_t<LB != 0, CompParamsBounded, CompParams>> p, DImg mip1, DImg mip3) {
     static_assert(!SP || ((LIGHTS || BL) && HIST), "SP: the LIGHTS / BL kernels' form of p.bloom_sparse (the render graph's launches)");
     static_assert(LB == 0 || (LIGHTS && (LB & kLbBounded)), "LB: forms of the lights kernels");
+    static_assert(!CS || (LB == 0 && !BL && !SP), "CS: cascades come without bounded lights, in-kernel bloom and zero cells");
     static_assert(!(LB & kLbCount) || (!BL && !SP), "the counting forms are the stand-alone calls'");
     constexpr bool CULL = (LB & kLbCull) != 0;
     LightArgs la = {};
@@ -468,6 +592,8 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
         f3 alb[2], nrm[2], wps[2];
         if constexpr (CULL) nrm[0] = nrm[1] = wps[0] = wps[1] = f3{0.0f, 0.0f, 0.0f};   // a lane outside the image rides along
         uint32_t lit = 0u;
+        [[maybe_unused]] d3 cw[2] = {d3{0.0, 0.0, 0.0}, d3{0.0, 0.0, 0.0}};           // CS: a lit pixel's world position
+        [[maybe_unused]] int ck[2] = {0, 0};                                          // ... and its cascade
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             if (CULL && !inside) continue;   // stays unlit and unwritten
@@ -490,6 +616,14 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
                 c = f4{cl.x, cl.y, cl.z, 1.0f};
             } else {
                 const float ao = (SOC_COMP_PROFILE & 2) ? u : (NT & 4) ? aop[k] : sample_r8(bo, u, v);
+                if constexpr (CS) {   // the shadow follows below, cascade by cascade for the whole wave
+                    pre[k] = shade_pre_unshadowed(p, f3{em.x, em.y, em.z}, f3{nn.x, nn.y, nn.z}, ao);
+                    alb[k] = f3{al.x, al.y, al.z};
+                    cw[k] = world_d(p, x + k, y, d);
+                    ck[k] = cascade_of(p, d);
+                    lit |= 1u << k;
+                    continue;
+                }
                 if (LIGHTS) {
                     pre[k] = shade_pre(p, u, v, d, f3{em.x, em.y, em.z}, f3{nn.x, nn.y, nn.z}, ao, bs);
                     alb[k] = f3{al.x, al.y, al.z};
@@ -499,6 +633,17 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
                 c = shade<false>(p, u, v, d, f3{al.x, al.y, al.z}, f3{em.x, em.y, em.z}, f3{nn.x, nn.y, nn.z}, ao, bs);
             }
             outp[k] = pack_h4(c);
+        }
+        if constexpr (CS) {
+            const bool live[2] = {(lit & 1u) != 0u, (lit & 2u) != 0u};
+            float sun[2] = {0.0f, 0.0f};
+            cascade_shadows<2>(p, live, ck, cw, bs, sun);
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (live[k]) {
+                    pre[k].direct *= sun[k];
+                    if (!LIGHTS) outp[k] = pack_h4(shade_post(p, pre[k], alb[k], nullptr));
+                }
         }
         // CULL, all 64 lanes here: the box of the wave's lit pixels (fminf drops a NaN coordinate: such a pixel fails every
         // bounded light's own test as well)
@@ -653,6 +798,39 @@ __global__ __launch_bounds__(kWorkgroup) void composition_generic_bounded(DImg t
     composition_generic_body<kLbBounded>(target, albedo, emissive, normal, depth, ssao, shadow, clouds, p, lb);
 }
 
+// cascaded sun shadows off the pair path: a pixel per lane, the wave's cascades walked as in composition_pair
+__global__ __launch_bounds__(kWorkgroup) void composition_generic_cascaded(DImg target, DImg albedo, DImg emissive, DImg normal,
+                                                           DImg depth, DImg ssao, DImg shadow, DImg clouds, CompParamsCascaded p) {
+    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+    if (x >= target.w || y >= target.h) return;
+    const float u = centre_uv(x, target.w), v = centre_uv(y, target.h);
+    const float d = sample_f32(depth, u, v);
+    const bool live = !(d == 1.0f);
+    const int ck = cascade_of(p, d);
+    const d3 w = world_d(p, x, y, d);
+    float sun = 0.0f;
+    cascade_shadows<1>(p, &live, &ck, &w, shadow, &sun);
+    f4 c;
+    if (!live) {
+        const f4 cl = sample_rgba8(clouds, u, v);
+        c = f4{cl.x, cl.y, cl.z, 1.0f};
+    } else {
+        const f4 al = sample_h4(albedo, u, v), em = sample_h4(emissive, u, v), nn = sample_h4(normal, u, v);
+        ShadePre s = shade_pre_unshadowed(p, f3{em.x, em.y, em.z}, f3{nn.x, nn.y, nn.z}, sample_r8(ssao, u, v));
+        s.direct *= sun;
+        if (p.npl | p.nsl) {   // shade<true>'s lights
+            const f3 wp = world_pos(p, u, v, d);
+            const V3<float> ls = light_sum<0>(p.dg, p.npl, p.nsl, V3<float>{nn.x, nn.y, nn.z}, V3<float>{wp.x, wp.y, wp.z},
+                                              mk3(p.cam[0], p.cam[1], p.cam[2]));
+            const f3 l3 = f3{ls.x, ls.y, ls.z};
+            c = shade_post(p, s, f3{al.x, al.y, al.z}, &l3);
+        } else {
+            c = shade_post(p, s, f3{al.x, al.y, al.z}, nullptr);
+        }
+    }
+    row_ptr_w<uint2>(target, y)[x] = pack_h4(c);
+}
+
 bool aligned16(const soc_img& im) {
     return (reinterpret_cast<uintptr_t>(im.data) & 15u) == 0 && (im.pitch_bytes & 15) == 0;
 }
@@ -677,6 +855,28 @@ PairBounded pair_bounded(int lb) {
 // what a bounded call adds to composition_launch's arguments (null: the unbounded kernels)
 using BoundedCall = soc::LightBoundsCall;
 
+// The cascaded instantiations' parameter block: the record's matrices (and the camera's inverses) widened to fp64, the
+// factors as they are (the unused entries repeat the last cascade) and +inf for the splits that do not exist.
+CompParamsCascaded cascaded_params(const CompParams& p, const soc_sun_cascades& cs, int W, int H) {
+    CompParamsCascaded pc;
+    static_cast<CompParams&>(pc) = p;
+    pc.count = cs.count;
+    pc.S = cs.map_size;
+    for (int i = 0; i < 16; ++i) {
+        pc.inv_proj_d.m[i] = (double)p.inv_proj.m[i];
+        pc.inv_view_d.m[i] = (double)p.inv_view.m[i];
+    }
+    pc.rw_d = 1.0 / (double)W;
+    pc.rh_d = 1.0 / (double)H;
+    for (int k = 0; k < SOC_MAX_SUN_CASCADES; ++k) {
+        const int c = k < cs.count ? k : cs.count - 1;
+        for (int i = 0; i < 16; ++i) pc.pv[k].m[i] = (double)cs.projection_view[c][i];
+        pc.ef[k] = cs.exponential_factor[c];
+        if (k < SOC_MAX_SUN_CASCADES - 1) pc.split[k] = k < cs.count - 1 ? cs.split_depth[k] : __builtin_inff();
+    }
+    return pc;
+}
+
 // bins != nullptr: the fused histogram variant if the pair path applies at the globals' resolution
 // (returns 1 otherwise, having launched nothing)
 // bloom_mip1 != nullptr (the render graph under SOC_RENDERER_BLOOM_IN_COMPOSITION): the bloom output is computed in the
@@ -687,10 +887,18 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
                        soc_img normal, soc_img depth, soc_img ssao, soc_img shadow, soc_img clouds, uint32_t* bins,
                        uint32_t* scratch, soc_stream stream, bool fold = true, bool sky_external = false,
                        const soc_img* bloom_mip1 = nullptr, const soc_img* bloom_mip3 = nullptr,
-                       const BoundedCall* bc = nullptr) {
+                       const BoundedCall* bc = nullptr, const soc_sun_cascades* cs = nullptr, bool cascaded = false) {
     static const char* P = "soc_composition";
     if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
-    int rc = check_img(target, SOC_FMT_RGBA16F, P, "target");
+    int rc = SOC_OK;
+    if (cascaded) {   // the record and its atlas first, so that the message names the cascades' field
+        rc = check_sun_cascades(cs, &shadow, P);
+        if (rc) return rc;
+        if (bc) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with bounded lights are not supported", P);
+        if (bloom_mip1) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with the in-kernel bloom are not supported", P);
+        if (bloom_mip3) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with the bloom's zero cells are not supported", P);
+    }
+    rc = check_img(target, SOC_FMT_RGBA16F, P, "target");
     if (!rc) rc = check_img(albedo, SOC_FMT_RGBA16F, P, "albedo");
     if (!rc) rc = check_img(emissive, SOC_FMT_RGBA16F, P, "emissive");
     if (!rc) rc = check_img(normal, SOC_FMT_RGBA16F, P, "normal");
@@ -771,6 +979,25 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
             else kb = pair_bounded<true, false, false>(lb);
             if (!kb) return set_error(SOC_E_INVALID_ARG, "%s: the shaded-pairs counter is the stand-alone calls'", P);
         }
+        if (cascaded) {   // the pair path's cascaded forms: with and without the histogram, with and without lights
+            if (bins) {
+                p.bins = scratch;
+                p.sky_external = sky_external ? 1 : 0;
+                p.lmin = g->log_min_luminance;
+                p.lrange = g->log_max_luminance - g->log_min_luminance;
+                p.bf = bin_fast_params(p.lmin, p.lrange);
+            }
+            const CompParamsCascaded pc = cascaded_params(p, *cs, W, H);
+#define SOC_COMP_PAIR_CS(HI, LI, N) launch("composition_pair", kWorkgroup, composition_pair<HI, LI, N, false, false, 0, true>, grd, kWorkgroup, 0, \
+            hs(stream), dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), pc, DImg{}, DImg{})
+            if (bins && lights) SOC_COMP_PAIR_CS(true, true, 0);
+            else if (bins) SOC_COMP_PAIR_CS(true, false, 7);
+            else if (lights) SOC_COMP_PAIR_CS(false, true, 0);
+            else SOC_COMP_PAIR_CS(false, false, 7);
+#undef SOC_COMP_PAIR_CS
+            if (bins && fold) launch("histogram_fold", kBins, histogram_fold, 1, kBins, 0, hs(stream), scratch, bins);
+            return check_launch("composition");
+        }
         auto launch_bounded = [&](const DImg& m1) {
             CompParamsBounded pb;
             static_cast<CompParams&>(pb) = p;
@@ -834,7 +1061,11 @@ int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_i
 #undef SOC_COMP_PAIR
     } else {
         dim3 blk(BX, BY), grd(ceil_div(W, BX), ceil_div(H, BY));
-        if (bc && (p.npl | p.nsl))
+        if (cascaded)
+            launch("composition_generic_cascaded", kWorkgroup, composition_generic_cascaded, grd, blk, 0, hs(stream), dimg(target),
+                   dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds),
+                   cascaded_params(p, *cs, W, H));
+        else if (bc && (p.npl | p.nsl))
             launch("composition_generic_bounded", kWorkgroup, composition_generic_bounded, grd, blk, 0, hs(stream), dimg(target),
                    dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p,
                    static_cast<const LightBoundsDev*>(bc->d_bounds));
@@ -900,19 +1131,22 @@ int soc::composition_luminance_histogram(const soc_globals* g, const soc_globals
                                          soc_img albedo, soc_img emissive, soc_img normal, soc_img depth, soc_img ssao,
                                          soc_img shadow, soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch,
                                          bool fold, soc_stream stream, bool sky_external, const soc_img* bloom_mip1,
-                                         const soc_img* bloom_mip3, const LightBoundsCall* bounds) {
+                                         const soc_img* bloom_mip3, const LightBoundsCall* bounds,
+                                         const soc_sun_cascades* cascades) {
     if (!g || !ae || !scratch)
         return set_error(SOC_E_INVALID_ARG, "soc_composition_luminance_histogram: null globals / auto exposure / scratch");
     const BoundedCall* bc = bounds;
+    const bool cs = cascades != nullptr;
     int rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds,
-                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1, bloom_mip3, bc);
+                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1, bloom_mip3, bc,
+                                cascades, cs);
     if (rc <= 0) return rc;   // launched (or failed validation)
     if (bloom_mip3) return set_error(SOC_E_SHAPE, "composition: the bloom's zero cells need the pair path");
     if (bloom_mip1) return set_error(SOC_E_SHAPE, "composition: the in-kernel bloom needs the pair path");
     if (sky_external) return set_error(SOC_E_INVALID_ARG, "composition: sky_external needs the pair path");
     // not fusable: the two passes back to back (same results)
     rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
-                            stream, true, false, nullptr, nullptr, bc);
+                            stream, true, false, nullptr, nullptr, bc, cascades, cs);
     if (rc) return rc;
     return soc_generate_luminance_histogram(g, target, ae, stream);
 }
@@ -939,4 +1173,21 @@ extern "C" int soc_composition_luminance_histogram_bounded(const soc_globals* g,
     const LightBoundsCall bc = {d_bounds, flags, d_shaded_pairs};
     return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
                                            scratch, true, stream, false, nullptr, nullptr, &bc);
+}
+
+extern "C" int soc_composition_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                                        soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                                        soc_img clouds, const soc_sun_cascades* cascades, soc_stream stream) {
+    return composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
+                              stream, true, false, nullptr, nullptr, nullptr, cascades, true);
+}
+
+extern "C" int soc_composition_luminance_histogram_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target,
+                                                            soc_img albedo, soc_img emissive, soc_img normal, soc_img depth,
+                                                            soc_img ssao, soc_img shadow, soc_img clouds, soc_auto_exposure* ae,
+                                                            uint32_t* scratch, const soc_sun_cascades* cascades,
+                                                            soc_stream stream) {
+    if (!cascades) return set_error(SOC_E_INVALID_ARG, "soc_composition_luminance_histogram_cascaded: null cascades");
+    return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
+                                           scratch, true, stream, false, nullptr, nullptr, nullptr, cascades);
 }

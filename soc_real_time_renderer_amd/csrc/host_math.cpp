@@ -470,3 +470,143 @@ extern "C" int soc_upload_light_bounds(const soc_light_bounds* host, void* d_bou
     if (e != hipSuccess) return set_error(SOC_E_HIP, "soc_upload_light_bounds: %s", hipGetErrorString(e));
     return SOC_OK;
 }
+
+// =================================================================================================
+// Cascaded sun shadow maps (soc_rt.h): the record's validation and the fit. Host fp32, no HIP call.
+// =================================================================================================
+int soc::check_sun_cascades(const soc_sun_cascades* c, const soc_img* atlas, const char* P) {
+    if (!c) return set_error(SOC_E_INVALID_ARG, "%s: null cascades", P);
+    if (c->count < 1 || c->count > SOC_MAX_SUN_CASCADES)
+        return set_error(SOC_E_INVALID_ARG, "%s: cascades count = %d (1..%d)", P, c->count, SOC_MAX_SUN_CASCADES);
+    if (c->map_size < 2) return set_error(SOC_E_INVALID_ARG, "%s: cascades map_size = %d (>= 2)", P, c->map_size);
+    if (c->map_size > 16384) return set_error(SOC_E_INVALID_ARG, "%s: cascades map_size = %d (<= 16384)", P, c->map_size);
+    for (int k = 0; k < c->count; ++k) {
+        for (int i = 0; i < 16; ++i)
+            if (!std::isfinite(c->projection_view[k][i]))
+                return set_error(SOC_E_INVALID_ARG, "%s: cascades projection_view[%d][%d] is not finite", P, k, i);
+        if (!std::isfinite(c->exponential_factor[k]))
+            return set_error(SOC_E_INVALID_ARG, "%s: cascades exponential_factor[%d] is not finite", P, k);
+    }
+    for (int i = 0; i + 1 < c->count; ++i) {
+        if (!std::isfinite(c->split_depth[i]))
+            return set_error(SOC_E_INVALID_ARG, "%s: cascades split_depth[%d] is not finite", P, i);
+        if (i > 0 && !(c->split_depth[i] > c->split_depth[i - 1]))
+            return set_error(SOC_E_INVALID_ARG, "%s: cascades split_depth[%d] = %g is not above split_depth[%d] = %g", P, i,
+                             (double)c->split_depth[i], i - 1, (double)c->split_depth[i - 1]);
+    }
+    if (atlas) {
+        if (atlas->format != SOC_FMT_D32F)
+            return set_error(SOC_E_INVALID_ARG, "%s: cascades atlas format %d is not D32F", P, atlas->format);
+        if (atlas->width != c->map_size || (int64_t)atlas->height != (int64_t)c->count * c->map_size)
+            return set_error(SOC_E_INVALID_ARG, "%s: cascades atlas extent %dx%d is not map_size x count*map_size = %dx%d", P,
+                             atlas->width, atlas->height, c->map_size, c->count * c->map_size);
+    }
+    return SOC_OK;
+}
+
+extern "C" int soc_sun_cascades_from_sun(const soc_globals* g, int32_t map_size, soc_sun_cascades* out) {
+    static const char* P = "soc_sun_cascades_from_sun";
+    if (!g || !out) return set_error(SOC_E_INVALID_ARG, "%s: null argument", P);
+    if (map_size < 2) return set_error(SOC_E_INVALID_ARG, "%s: map_size = %d (>= 2)", P, map_size);
+    soc_sun_cascades c;
+    std::memset(&c, 0, sizeof c);
+    c.count = 1;
+    c.map_size = map_size;
+    mat4_mul_host(c.projection_view[0], g->sun_info.projection_matrix, g->sun_info.view_matrix);
+    c.exponential_factor[0] = g->sun_info.exponential_factor;
+    const int rc = check_sun_cascades(&c, nullptr, P);
+    if (rc) return rc;
+    *out = c;
+    return SOC_OK;
+}
+
+// The radius quantum of a cascade's bounding sphere (world units): the orthographic extent only takes multiples of it.
+static const float kCascadeRadiusQuantum = 0.125f;
+
+extern "C" int soc_sun_cascades_fit(const soc_globals* g, int32_t count, int32_t map_size, float near_distance,
+                                    float max_distance, float split_lambda, float caster_margin, soc_sun_cascades* out) {
+    static const char* P = "soc_sun_cascades_fit";
+    if (!g || !out) return set_error(SOC_E_INVALID_ARG, "%s: null argument", P);
+    if (count < 1 || count > SOC_MAX_SUN_CASCADES)
+        return set_error(SOC_E_INVALID_ARG, "%s: count = %d (1..%d)", P, count, SOC_MAX_SUN_CASCADES);
+    if (map_size < 2 || map_size > 16384) return set_error(SOC_E_INVALID_ARG, "%s: map_size = %d (2..16384)", P, map_size);
+    if (!std::isfinite(near_distance) || !std::isfinite(max_distance) || !(near_distance > 0.0f) || !(max_distance > near_distance))
+        return set_error(SOC_E_INVALID_ARG, "%s: near_distance = %g, max_distance = %g (0 < near < max, finite)", P,
+                         (double)near_distance, (double)max_distance);
+    if (!(split_lambda >= 0.0f && split_lambda <= 1.0f))
+        return set_error(SOC_E_INVALID_ARG, "%s: split_lambda = %g (0..1)", P, (double)split_lambda);
+    if (!(caster_margin >= 0.0f) || !std::isfinite(caster_margin))
+        return set_error(SOC_E_INVALID_ARG, "%s: caster_margin = %g (finite, >= 0)", P, (double)caster_margin);
+    // the camera's projection without the frame's jitter (application.cpp:113-131 adds it to proj[3][0..1])
+    float pj[16];
+    std::memcpy(pj, g->camera_projection_matrix, sizeof pj);
+    pj[12] -= g->jitter[0];
+    pj[13] -= g->jitter[1];
+    if (pj[0] == 0.0f || pj[5] == 0.0f) return set_error(SOC_E_INVALID_ARG, "%s: the globals hold no camera projection", P);
+    soc_sun_cascades c;
+    std::memset(&c, 0, sizeof c);
+    c.count = count;
+    c.map_size = map_size;
+    // slice distances
+    float dist[SOC_MAX_SUN_CASCADES + 1];
+    dist[0] = near_distance;
+    const float n = near_distance, f = max_distance, N = (float)count;
+    for (int i = 1; i <= count; ++i) {
+        const float t = (float)i / N;
+        dist[i] = i == count ? f : split_lambda * (n * std::pow(f / n, t)) + (1.0f - split_lambda) * (n + (f - n) * t);
+    }
+    for (int i = 0; i + 1 < count; ++i) {   // the depth-buffer value of (0, 0, -d, 1): z only
+        const float z = -dist[i + 1];
+        c.split_depth[i] = (pj[10] * z + pj[14]) / (pj[11] * z + pj[15]);
+    }
+    // the light's rotation: lookAt from the origin along the sun's direction, the reference's up (renderer.cpp:126)
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, up[3] = {0.0f, -1.0f, 0.0f};
+    float rot[16];
+    soc_mat4_look_at_rh(rot, zero, g->sun_info.direction, up);
+    rot[12] = rot[13] = rot[14] = 0.0f;   // -dot(s, 0): -0
+    const float S = (float)map_size;
+    for (int k = 0; k < count; ++k) {
+        // the slice's eight corners in view space, their centroid and the bounding sphere around it: all of it depends
+        // on the projection and the distances only, so neither a rotation nor a translation of the camera changes it
+        V3h corner[8];
+        V3h mid{0.0f, 0.0f, 0.0f};
+        for (int j = 0; j < 8; ++j) {
+            const float z = -dist[k + (j >> 2)];
+            const float w = pj[11] * z + pj[15];
+            const float sx = (j & 1) ? 1.0f : -1.0f, sy = (j & 2) ? 1.0f : -1.0f;
+            corner[j] = V3h{(sx * w - pj[8] * z - pj[12]) / pj[0], (sy * w - pj[9] * z - pj[13]) / pj[5], z};
+            mid = V3h{mid.x + corner[j].x, mid.y + corner[j].y, mid.z + corner[j].z};
+        }
+        mid = V3h{mid.x * 0.125f, mid.y * 0.125f, mid.z * 0.125f};
+        float r2 = 0.0f;
+        for (int j = 0; j < 8; ++j) {
+            const V3h d = sub(corner[j], mid);
+            r2 = std::fmax(r2, dot(d, d));
+        }
+        // room for the snap (at most half a texel = R / S per axis) and for fp32, then up to the quantum
+        const float need = std::sqrt(r2) / (1.0f - 1.0f / S) * 1.00001f;
+        const float R = std::ceil(need / kCascadeRadiusQuantum) * kCascadeRadiusQuantum;
+        const float D = 2.0f * R + caster_margin;   // the depth range that lands in z_ndc [0, 1] (quirk Q1: the raster keeps that half)
+        float proj[16];
+        soc_mat4_ortho_rh_no(proj, -R, R, -R, R, -D, D);
+        // the centre in world and in light space; x and y snapped to whole texels, z so that the sphere and caster_margin
+        // towards the sun sit in view z [-D, 0]
+        const float* iv = g->camera_inverse_view_matrix;
+        const V3h cw{iv[0] * mid.x + iv[4] * mid.y + iv[8] * mid.z + iv[12], iv[1] * mid.x + iv[5] * mid.y + iv[9] * mid.z + iv[13],
+                     iv[2] * mid.x + iv[6] * mid.y + iv[10] * mid.z + iv[14]};
+        const V3h cl{rot[0] * cw.x + rot[4] * cw.y + rot[8] * cw.z, rot[1] * cw.x + rot[5] * cw.y + rot[9] * cw.z,
+                     rot[2] * cw.x + rot[6] * cw.y + rot[10] * cw.z};
+        const float texel = (2.0f * R) / S;
+        float view[16];
+        std::memcpy(view, rot, sizeof view);
+        view[12] = -(std::floor(cl.x / texel + 0.5f) * texel);
+        view[13] = -(std::floor(cl.y / texel + 0.5f) * texel);
+        view[14] = -(R + caster_margin) - cl.z;
+        mat4_mul_host(c.projection_view[k], proj, view);
+        c.exponential_factor[k] = g->sun_info.exponential_factor * g->sun_info.projection_matrix[10] / proj[10];
+    }
+    const int rc = check_sun_cascades(&c, nullptr, P);
+    if (rc) return rc;
+    *out = c;
+    return SOC_OK;
+}

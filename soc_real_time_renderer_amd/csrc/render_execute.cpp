@@ -489,6 +489,8 @@ static void frame_done(soc_renderer* r, int phase) {
     if (phase & SOC_PHASE_POST_EXPOSURE) r->hist = 1 - r->hist;   // ping-pong the TAA history
 }
 
+static int cascades_conflict(const soc_renderer* r, const char* who);
+
 static int ssao_first(const soc_renderer* r) { return tuning_knob("SOC_RENDERER_SSAO_FIRST", r->bloom_sparse_frame ? 0 : -1); }
 
 extern "C" int soc_renderer_execute(soc_renderer* r, const soc_globals* g, int32_t phase, soc_stream stream) {
@@ -496,6 +498,10 @@ extern "C" int soc_renderer_execute(soc_renderer* r, const soc_globals* g, int32
     hipStream_t s = hs(stream);
     const bool pre = phase & SOC_PHASE_PRE_EXPOSURE;
     int rc = frame_facts(r, g, phase);
+    if (!rc && pre && r->has_cascades) {   // the atlas and the settings again: either may have changed since the record was set
+        rc = soc::check_sun_cascades(&r->cascades, &r->img.shadow, "soc_renderer_execute");
+        if (!rc) rc = cascades_conflict(r, "soc_renderer_execute");
+    }
     // the fused histogram's partial copies, cleared on `s`
     if (!rc && pre && !(r->flags & SOC_RENDERER_UNFUSED_HISTOGRAM)) rc = ensure_hist_scratch(r, s);
     if (!rc && pre && (g->point_light_count || g->spot_light_count)) rc = upload_lights(r, g, s);
@@ -675,6 +681,30 @@ extern "C" int soc_renderer_set_light_bounds(soc_renderer* r, const void* d_boun
     if (flags & ~(uint32_t)SOC_LIGHTS_CULL) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_light_bounds: unknown flags %u", flags);
     r->light_bounds = d_bounds;
     r->light_flags = d_bounds ? flags : 0u;
+    return SOC_OK;
+}
+
+// What cascades cannot be combined with (the cascaded kernels have no such forms), by name.
+static int cascades_conflict(const soc_renderer* r, const char* who) {
+    if (r->light_bounds) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with bounded lights (soc_renderer_set_light_bounds) are not supported", who);
+    if (r->flags & SOC_RENDERER_BLOOM_IN_COMPOSITION)   // the setting itself, whether or not it applies to this graph's extents
+        return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with SOC_RENDERER_BLOOM_IN_COMPOSITION are not supported", who);
+    return SOC_OK;
+}
+
+extern "C" int soc_renderer_set_sun_cascades(soc_renderer* r, const soc_sun_cascades* cascades) {
+    static const char* P = "soc_renderer_set_sun_cascades";
+    if (!r) return set_error(SOC_E_INVALID_ARG, "%s: null renderer", P);
+    if (!cascades) {
+        r->has_cascades = false;
+        return SOC_OK;
+    }
+    if (!r->img.shadow.data) return set_error(SOC_E_INVALID_ARG, "%s: sun cascades need images.shadow (the atlas)", P);
+    int rc = soc::check_sun_cascades(cascades, &r->img.shadow, P);
+    if (!rc) rc = cascades_conflict(r, P);
+    if (rc) return rc;
+    r->cascades = *cascades;
+    r->has_cascades = true;
     return SOC_OK;
 }
 

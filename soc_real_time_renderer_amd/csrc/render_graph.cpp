@@ -69,6 +69,17 @@ void build_raster_passes(soc_renderer* r) {
     if (r->scene.shadow)
         add_pass(r, "SunShadowDraw", "Shadows", pre, 0, res_mask({SOC_RES_SUN_SHADOW}),
                  [r, shadow_lane](const soc_globals* g, hipStream_t s) {
+                     if (r->has_cascades) {   // every cascade into its slab of the atlas, same cull and bias
+                         for (int k = 0; k < r->cascades.count; ++k) {
+                             const float* pv = r->cascades.projection_view[k];
+                             const int rc = r->has_draws
+                                 ? soc_raster_depth_draws(&r->draw_scene, pv, SOC_CULL_BACK, 1.25f, 1.75f, r->cascade_slab(k), (soc_stream)s)
+                                 : soc_raster_depth(&r->scene.mesh, pv, SOC_CULL_BACK, 1.25f, 1.75f, r->cascade_slab(k),
+                                                    shadow_lane ? r->shadow_ws : r->scene.workspace, (soc_stream)s);
+                             if (rc) return rc;
+                         }
+                         return (int)SOC_OK;
+                     }
                      if (r->has_draws)
                          return soc_raster_depth_draws(&r->draw_scene, g->sun_info.projection_view_matrix, SOC_CULL_BACK,
                                                        1.25f, 1.75f, r->img.shadow, (soc_stream)s);
@@ -83,6 +94,15 @@ void build_raster_passes(soc_renderer* r) {
         const bool head_shadow = r->scene.shadow != 0;
         add_pass(r, "SunShadowDrawTerrain", "Shadows", pre, res_mask({SOC_RES_SUN_SHADOW}), res_mask({SOC_RES_SUN_SHADOW}),
                  [r, head_shadow](const soc_globals* g, hipStream_t s) {
+                     if (r->has_cascades) {   // the terrain into every slab, unbiased, with the same clear rule
+                         for (int k = 0; k < r->cascades.count; ++k) {
+                             const int rc = soc_sun_shadow_draw_terrain(&r->terrain.shadow_mesh, r->cascades.projection_view[k],
+                                                                        head_shadow ? 0 : 1, r->cascade_slab(k),
+                                                                        r->terrain.shadow_workspace, (soc_stream)s);
+                             if (rc) return rc;
+                         }
+                         return (int)SOC_OK;
+                     }
                      return soc_sun_shadow_draw_terrain(&r->terrain.shadow_mesh, g->sun_info.projection_view_matrix,
                                                         head_shadow ? 0 : 1, r->img.shadow, r->terrain.shadow_workspace,
                                                         (soc_stream)s);
@@ -256,7 +276,8 @@ void build_passes_tail(soc_renderer* r) {
                                                                  r->sky_split_active,
                                                                  bloom_in_comp_active(r) ? &I.bloom_mips[1] : nullptr,
                                                                  r->bloom_cells_frame ? &I.bloom_mips[3] : nullptr,
-                                                                 r->light_bounds ? &lb : nullptr);
+                                                                 r->light_bounds ? &lb : nullptr,
+                                                                 r->has_cascades ? &r->cascades : nullptr);
                  });
         // the 8 partial histograms of the fused launch into the AutoExposure bins. Before a multi-GPU exchange
         // (PRE and POST in separate calls) the fold must precede it; in a one-call frame the resolve folds them
@@ -272,6 +293,9 @@ void build_passes_tail(soc_renderer* r) {
         add_pass(r, "Composition", "Composition", pre, comp_reads, res_mask({SOC_RES_COLOR}),
                  [r](const soc_globals* g, hipStream_t s) {
                      const auto& I = r->img;
+                     if (r->has_cascades)
+                         return soc_composition_cascaded(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
+                                                         I.ssao_blur, I.shadow, I.clouds, &r->cascades, (soc_stream)s);
                      if (r->light_bounds)
                          return soc_composition_bounded(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
                                                         I.ssao_blur, I.shadow, I.clouds, r->light_bounds, r->light_flags, nullptr,

@@ -102,6 +102,17 @@ struct soc_renderer {
     // soc_renderer_set_light_bounds: Composition launches the bounded kernels on this device record (null: unbounded)
     const void* light_bounds = nullptr;
     uint32_t light_flags = 0;
+    // soc_renderer_set_sun_cascades: a copy of the record; img.shadow is then its atlas, the shadow passes draw every
+    // cascade into its slab and Composition launches the cascaded call
+    soc_sun_cascades cascades{};
+    bool has_cascades = false;
+    // slab k of the atlas as an image of its own (rows [k * S, (k + 1) * S))
+    soc_img cascade_slab(int k) const {
+        soc_img s = img.shadow;
+        s.data = static_cast<char*>(s.data) + (size_t)k * (size_t)cascades.map_size * (size_t)s.pitch_bytes;
+        s.height = cascades.map_size;
+        return s;
+    }
     // pinned staging ring for the device globals upload (lights)
     soc_globals* staging = nullptr;
     hipEvent_t staging_ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -20,7 +20,7 @@ from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, FMT_RGBA8_SRGB, FMT_RGBA8_U
                    MATERIAL_NORMAL_MAP, MATERIAL_NORMAL_TEXTURE, MATERIAL_PAIRED_TEXELS, MATERIAL_ZERO_VELOCITY, Material, Mesh,
                    SocImg)
 
-__all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "MATERIAL_ZERO_VELOCITY", "MeshBuffers", "MipTexture", "material",
+__all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "sun_shadow_draw_cascades", "MATERIAL_ZERO_VELOCITY", "MeshBuffers", "MipTexture", "material",
            "normal_matrix", "materials_device", "raster_visibility", "raster_depth", "gbuffer_resolve",
            "SHADOW_BIAS_CONSTANT", "SHADOW_BIAS_SLOPE", "DrawScene", "draw", "transforms_device", "update_transforms",
            "raster_visibility_draws", "raster_depth_draws", "gbuffer_resolve_draws",
@@ -216,6 +216,17 @@ def raster_depth(mesh: MeshBuffers, view_projection, cull, depth: torch.Tensor, 
     vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
     _check(lib().soc_raster_depth(C.byref(mesh.struct), vp, int(cull), float(bias_constant), float(bias_slope),
                                   img(depth), _ptr(workspace), _stream(stream)), "raster_depth")
+
+
+def sun_shadow_draw_cascades(mesh: MeshBuffers, record, atlas: torch.Tensor, workspace: torch.Tensor, stream=None):
+    """SunShadowDraw of every cascade of a soc_sun_cascades record into its slab of the atlas (rows [k S, (k + 1) S)):
+    raster_depth per slab with projection_view[k], cull BACK and the reference's shadow bias."""
+    S = int(record.map_size)
+    if tuple(atlas.shape) != (int(record.count) * S, S):
+        raise ValueError(f"atlas {tuple(atlas.shape)} is not ({int(record.count) * S}, {S})")
+    for k in range(int(record.count)):
+        raster_depth(mesh, list(record.projection_view[k]), CULL_BACK, atlas[k * S:(k + 1) * S], workspace,
+                     bias_constant=1.25, bias_slope=1.75, stream=stream)
 
 
 def gbuffer_resolve(g, mesh: MeshBuffers, d_materials: torch.Tensor, material_count: int, visibility: torch.Tensor,
