@@ -761,7 +761,8 @@ typedef struct soc_material {
     float albedo_factor[4], emissive_factor[4];
     int32_t flags;                     /* SOC_MATERIAL_* */
     int32_t has_emissive;              /* 0: emissive = 0 (has_emissive_image) */
-    int32_t pad[2];
+    float alpha_cutoff;                /* with SOC_MATERIAL_ALPHA_MASK: the glTF alphaCutoff ("Alpha-masked materials") */
+    int32_t pad;
     soc_img normal_map;                /* RGBA16F, used with SOC_MATERIAL_NORMAL_MAP */
     soc_img normal_image;              /* RGBA8_UNORM tangent-space normal texture, with SOC_MATERIAL_NORMAL_TEXTURE */
     float max_anisotropy;              /* with SOC_MATERIAL_MIPMAPPED: 16 in the reference (texture.cpp:129-130) */
@@ -791,6 +792,9 @@ typedef struct soc_material {
 /* paired_texels holds the soc_pair_textures buffer of this material's albedo + normal_image (explicit opt-in: a caller
  * that fills the struct field by field without zeroing it never has stale padding read as a pointer) */
 #define SOC_MATERIAL_PAIRED_TEXELS 16
+/* glTF alphaMode MASK: a cutout material. Read ONLY by the *_masked raster calls ("Alpha-masked materials" below); every
+ * other entry point, the resolve included, ignores it. */
+#define SOC_MATERIAL_ALPHA_MASK 32
 
 #define SOC_CULL_NONE 0
 #define SOC_CULL_FRONT 1               /* depth prepass / G-buffer (depth_prepass.inl:45) */
@@ -957,6 +961,50 @@ int soc_gbuffer_resolve_draws(const soc_globals* g, const soc_draw_scene* scene,
  * also under SOC_RENDERER_STATIC_INPUTS (see there). */
 int soc_renderer_set_draw_scene(soc_renderer* r, const soc_draw_scene* scene, const soc_material* d_materials,
                                 int32_t material_count, int32_t shadow, uint64_t* visibility);
+
+/* --- Alpha-masked materials: cutout coverage (opt-in) --------------------------
+ * The reference has no alpha test (no `discard` in its shaders): a glTF alphaMode MASK material renders as solid
+ * geometry there and in every call above. The four *_masked calls are the raster calls' twins with a material table
+ * (device array, as the resolve takes it): a fragment of a triangle whose material has SOC_MATERIAL_ALPHA_MASK is kept
+ * or discarded by the test below after the coverage rules have accepted the pixel; a discarded fragment writes
+ * nothing (neither a key nor a depth). Triangles of other materials take the unmasked path, and a table without a
+ * flagged material gives the bits of the unmasked twin. The material of triangle t is
+ * min(mesh.materials[t], material_count - 1), 0 when mesh.materials is NULL (the resolve's clamp); for a draw scene
+ * the draw's material. All arithmetic is fp32, each operation rounded on its own (no contraction):
+ *   1. es = e0 + e1 + e2; b1 = e1 / es; b2 = e2 / es; b0 = 1 - b1 - b2, with e_i the raster's three edge values at the
+ *      pixel centre (the resolve's barycentrics, bit for bit);
+ *   2. u = b0 uvA.x + b1 uvB.x + b2 uvC.x, v likewise (the resolve's expression, in its order; a draw scene: the uvs of
+ *      the triangle's transformed-vertex slots);
+ *   3. LEVEL 0 of `albedo`, always, also under SOC_MATERIAL_MIPMAPPED and SOC_MATERIAL_PAIRED_TEXELS: REPEAT on each
+ *      axis with the sampling contract's 8-bit weights kx, ky (any extent, the image's pitch), the four texels' alpha
+ *      bytes, A = (a00 (256 - kx) + a10 kx) (256 - ky) + (a01 (256 - kx) + a11 kx) ky, an integer <= 255 * 65536;
+ *   4. alpha = (float)A * (1.0f / (255.0f * 65536.0f));
+ *   5. kept iff alpha * albedo_factor[3] >= alpha_cutoff. A NaN on either side discards. albedo.data == NULL: alpha 1.
+ * Level 0 is deliberate: uv derivatives do not exist before visibility is resolved, and level 0 keeps thin cutouts
+ * (a chain, a fence) from eroding with distance, which the averaged alpha of the lower levels does. The decision is
+ * exact by specification: results are compared bit for bit, without a tolerance. A visible fragment's G-buffer values
+ * do not depend on the test, so soc_gbuffer_resolve(_draws) reads a masked visibility buffer as it reads any other.
+ * alphaMode BLEND has no place in a deferred frame (one surface per pixel) and is rendered opaque.
+ * Errors, all before the first HIP call: the twin's, and SOC_E_INVALID_ARG for null d_materials, material_count <= 0,
+ * null uvs (mesh or scene), or (draw scenes) material_count < scene->material_count. Workspaces are the twins'. */
+int soc_raster_visibility_masked(const soc_mesh* mesh, const float view_projection[16], int32_t cull,
+                                 uint64_t* visibility, int32_t width, int32_t height, int32_t clear, void* workspace,
+                                 const soc_material* d_materials, int32_t material_count, soc_stream stream);
+int soc_raster_depth_masked(const soc_mesh* mesh, const float view_projection[16], int32_t cull, float bias_constant,
+                            float bias_slope, soc_img depth, void* workspace, const soc_material* d_materials,
+                            int32_t material_count, soc_stream stream);
+int soc_raster_visibility_draws_masked(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                       uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
+                                       const soc_material* d_materials, int32_t material_count, soc_stream stream);
+int soc_raster_depth_draws_masked(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                  float bias_constant, float bias_slope, soc_img depth, const soc_material* d_materials,
+                                  int32_t material_count, soc_stream stream);
+/* Render graph: with enable != 0 and a raster head set (mesh or draw scene), DepthPrepass and SunShadowDraw (every
+ * cascade slab included) call the masked twins with the head's own material table. A renderer flag: no HIP call, no
+ * pass is rebuilt; names, groups, lanes and declared uses stay, and the flag survives a change of head. The terrain
+ * layer's passes stay unmasked (the reference's terrain material is opaque; DrawTerrain depth-tests against the depth
+ * image and so sees the cutouts). SOC_E_INVALID_ARG: null renderer. */
+int soc_renderer_set_alpha_mask(soc_renderer* r, int32_t enable);
 
 /* --- Draw scenes: per-object motion vectors (opt-in) ----------------------------
  * The reference forms the previous clip position with the CURRENT model matrix, so the velocity of an entity that moved

@@ -649,6 +649,12 @@ class Renderer:
         _check(lib().soc_renderer_set_light_bounds(self.handle, _ptr(d_bounds), _abi.LIGHTS_CULL if cull else 0),
                "soc_renderer_set_light_bounds")
 
+    def set_alpha_mask(self, enable: bool) -> None:
+        """Cutout materials (SOC_MATERIAL_ALPHA_MASK, raster.material(alpha_mode="MASK")): with a raster head set,
+        DepthPrepass and SunShadowDraw (every cascade slab) run the alpha test with the head's material table. A flag:
+        no pass is rebuilt and it survives set_raster_scene / set_draw_scene."""
+        _check(lib().soc_renderer_set_alpha_mask(self.handle, int(bool(enable))), "soc_renderer_set_alpha_mask")
+
     def set_sun_cascades(self, record) -> None:
         """Cascaded sun shadows: the record is copied (refit and set it whenever the camera moves); the renderer's shadow
         image must be the record's atlas (sun_cascade_atlas). None: back to the one map."""

@@ -131,7 +131,7 @@ class Mesh(C.Structure):
 class Material(C.Structure):
     _fields_ = [("albedo", SocImg), ("emissive", SocImg), ("albedo_factor", C.c_float * 4),
                 ("emissive_factor", C.c_float * 4), ("flags", C.c_int32), ("has_emissive", C.c_int32),
-                ("pad", C.c_int32 * 2), ("normal_map", SocImg), ("normal_image", SocImg),
+                ("alpha_cutoff", C.c_float), ("pad", C.c_int32), ("normal_map", SocImg), ("normal_image", SocImg),
                 ("max_anisotropy", C.c_float), ("pad2", C.c_int32), ("paired_texels", C.c_void_p)]
 
 
@@ -203,6 +203,7 @@ MATERIAL_NORMAL_MAP = 2
 MATERIAL_NORMAL_TEXTURE = 4
 MATERIAL_MIPMAPPED = 8
 MATERIAL_PAIRED_TEXELS = 16
+MATERIAL_ALPHA_MASK = 32
 
 class LightBounds(C.Structure):
     """soc_light_bounds: a range per light, indexed like Globals.point_lights / spot_lights (0: unlimited)."""
@@ -345,6 +346,15 @@ FUNCTIONS = {
     "soc_draw_terrain": (_I, [_G, C.POINTER(Mesh), _P, C.c_int32, _P, _IMG, _IMG, _IMG, _IMG, _P, _P]),
     "soc_sun_shadow_draw_terrain": (_I, [C.POINTER(Mesh), C.POINTER(C.c_float), C.c_int32, _IMG, _P, _P]),
     "soc_renderer_set_terrain": (_I, [_P, C.POINTER(TerrainLayer)]),
+    "soc_raster_visibility_masked": (_I, [C.POINTER(Mesh), C.POINTER(C.c_float), C.c_int32, _P, C.c_int32, C.c_int32,
+                                          C.c_int32, _P, _P, C.c_int32, _P]),
+    "soc_raster_depth_masked": (_I, [C.POINTER(Mesh), C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float, _IMG, _P, _P,
+                                     C.c_int32, _P]),
+    "soc_raster_visibility_draws_masked": (_I, [C.POINTER(DrawSceneStruct), C.POINTER(C.c_float), C.c_int32, _P, C.c_int32,
+                                                C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "soc_raster_depth_draws_masked": (_I, [C.POINTER(DrawSceneStruct), C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float,
+                                           _IMG, _P, C.c_int32, _P]),
+    "soc_renderer_set_alpha_mask": (_I, [_P, C.c_int32]),
 }
 
 # not in the public header: test hooks

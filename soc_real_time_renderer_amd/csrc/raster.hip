@@ -237,8 +237,82 @@ __device__ __forceinline__ bool cover(const TriSetup& t, int x, int y, float& e0
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Alpha-masked materials (soc_rt.h "Alpha-masked materials"): the MASK forms of raster_small / raster_big
+// ------------------------------------------------------------------------------------------------
+// What a masked call adds to the two triangle kernels' arguments (the MASK = false forms take none of it).
+struct MaskTable {
+    const float* uvs;                // per vertex; a draw scene: per transformed-vertex slot
+    const uint32_t* tri_materials;   // per triangle, or null (all 0)
+    const soc_material* mats;
+    int material_count;
+};
+// A triangle's share of the test: whether its material is flagged and, then, the fields the test reads and the uvs.
+struct MaskTri {
+    bool on;
+    const char* data;   // level 0 of the albedo (null: alpha 1)
+    int w, h, pitch;
+    float cutoff, factor;
+    float ua, va, ub, vb, uc, vc;
+};
+__device__ __forceinline__ MaskTable mask_of() { return MaskTable{nullptr, nullptr, nullptr, 0}; }
+__device__ __forceinline__ MaskTable mask_of(const MaskTable& k) { return k; }
+
+// UNIFORM (raster_big: the wave works on one triangle): `id` is wave-uniform, the material index goes through
+// readfirstlane, so the index, material and uv fetches are scalar loads and the fields sit in SGPRs. Only the fields the
+// test needs are read, and of an unflagged material only `flags`.
+template <bool UNIFORM>
+__device__ __forceinline__ MaskTri load_mask(const MaskTable& k, const uint32_t* __restrict__ idx, int id) {
+    MaskTri m{};
+    uint32_t mi = k.tri_materials ? min(k.tri_materials[id], (uint32_t)(k.material_count - 1)) : 0u;
+    if (UNIFORM) mi = __builtin_amdgcn_readfirstlane(mi);
+    const soc_material& mat = k.mats[mi];
+    if (!(mat.flags & SOC_MATERIAL_ALPHA_MASK)) return m;
+    m.on = true;
+    m.data = static_cast<const char*>(mat.albedo.data);
+    m.w = mat.albedo.width;
+    m.h = mat.albedo.height;
+    m.pitch = mat.albedo.pitch_bytes;
+    m.cutoff = mat.alpha_cutoff;
+    m.factor = mat.albedo_factor[3];
+    const uint32_t a = idx[3 * id], b = idx[3 * id + 1], c = idx[3 * id + 2];
+    m.ua = k.uvs[2 * a]; m.va = k.uvs[2 * a + 1];
+    m.ub = k.uvs[2 * b]; m.vb = k.uvs[2 * b + 1];
+    m.uc = k.uvs[2 * c]; m.vc = k.uvs[2 * c + 1];
+    return m;
+}
+
+// Steps 1-5 of the contract for a covered fragment with edge values e0..e2: gbuffer_resolve's barycentrics and uv
+// (same operands, same order, so the same bits), the level-0 REPEAT axes, two row loads, the exact integer bilinear of
+// the four alpha bytes (<= 255 * 65536 < 2^24: the conversion is exact), one scale, one multiply, one compare.
+__device__ __forceinline__ bool alpha_keeps(const MaskTri& m, float e0, float e1, float e2) {
+#pragma clang fp contract(off)
+    float alpha = 1.0f;
+    if (m.data) {
+        const float es = e0 + e1 + e2;
+        const float b1 = e1 / es, b2 = e2 / es, b0 = 1.0f - b1 - b2;
+        const float u = b0 * m.ua + b1 * m.ub + b2 * m.uc;
+        const float v = b0 * m.va + b1 * m.vb + b2 * m.vc;
+        const DImg im{const_cast<char*>(m.data), m.w, m.h, m.pitch};
+        const Axis ax = axis_repeat_level(u, m.w), ay = axis_repeat_level(v, m.h);
+        uint32_t t00, t10, t01, t11;
+        texel_row_pair(im, ax.i0, ax.i1, ay.i0, t00, t10);
+        texel_row_pair(im, ax.i0, ax.i1, ay.i1, t01, t11);
+        const uint32_t kx = (uint32_t)(ax.w * 256.0f), ky = (uint32_t)(ay.w * 256.0f);
+        const uint32_t A = ((t00 >> 24) * (256u - kx) + (t10 >> 24) * kx) * (256u - ky) +
+                           ((t01 >> 24) * (256u - kx) + (t11 >> 24) * kx) * ky;
+        alpha = (float)A * (1.0f / (255.0f * 65536.0f));
+    }
+    return alpha * m.factor >= m.cutoff;   // a NaN on either side: false, the fragment is discarded
+}
+
+// MASK: a fragment of a flagged triangle first reads the pixel's current value with a plain load. Stored values only
+// decrease, so a stale (larger) value never skips a needed atomic; a value already below this fragment's key (depth-only:
+// not above its biased depth bits) means the fragment has lost whatever its alpha, and it leaves before the taps. Then
+// the test; a discarded fragment issues no atomic.
+template <bool MASK>
 __device__ __forceinline__ void shade(const TriSetup& t, int id, int x, int y, const RasterParams& p, void* target,
-                                      size_t pitch) {
+                                      size_t pitch, const MaskTri& mk) {
     float e0, e1, e2, z;
     if (!cover(t, x, y, e0, e1, e2, z)) return;
     // a plain load first: values only decrease, so a stale (larger) value never skips a needed atomic
@@ -247,10 +321,12 @@ __device__ __forceinline__ void shade(const TriSetup& t, int id, int x, int y, c
         const float zb = fminf(fmaxf(z + t.bias, 0.0f), 1.0f);
         uint32_t* d = reinterpret_cast<uint32_t*>(static_cast<char*>(target) + (size_t)y * pitch) + x;
         const uint32_t key = __float_as_uint(zb);
+        if (MASK && mk.on && (*d <= key || !alpha_keeps(mk, e0, e1, e2))) return;
         atomicMin(d, key);
     } else {
         const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(0xFFFFFFFEu - (uint32_t)id);
         unsigned long long* d = reinterpret_cast<unsigned long long*>(static_cast<char*>(target) + (size_t)y * pitch) + x;
+        if (MASK && mk.on && (*d < key || !alpha_keeps(mk, e0, e1, e2))) return;
         atomicMin(d, key);
     }
 }
@@ -288,8 +364,12 @@ __global__ __launch_bounds__(kWorkgroup) void raster_clear_depth(char* depth, si
 #ifndef SOC_RASTER_WG_ENTRIES
 #define SOC_RASTER_WG_ENTRIES 1
 #endif
+// MASK = true takes one more argument, the MaskTable (M is empty otherwise: the MASK = false kernels keep their
+// parameter lists and, as instantiations of these templates, their gfx950 instructions: profiles/alpha_mask_isa_identity.txt).
+// Here the material is per lane: a flagged triangle's fields and uvs are fetched once, before its pixel loop.
+template <bool MASK, typename... M>
 __global__ __launch_bounds__(kWorkgroup) void raster_small(const uint32_t* __restrict__ idx, Workspace ws, RasterParams p,
-                                                    void* target, size_t pitch) {
+                                                    void* target, size_t pitch, M... mask) {
     const int id = blockIdx.x * 256 + threadIdx.x;
     TriSetup t{};
     t.live = false;
@@ -320,8 +400,10 @@ __global__ __launch_bounds__(kWorkgroup) void raster_small(const uint32_t* __res
         return;
     }
     if (!t.live) return;
+    MaskTri mk{};
+    if (MASK) mk = load_mask<false>(mask_of(mask...), idx, id);
     for (int y = t.py0; y <= t.py1; ++y)
-        for (int x = t.px0; x <= t.px1; ++x) shade(t, id, x, y, p, target, pitch);
+        for (int x = t.px0; x <= t.px1; ++x) shade<MASK>(t, id, x, y, p, target, pitch, mk);
 }
 
 // Upper bound of the edge function over the pixel centres of [x0, x1] x [y0, y1] (a corner), minus a
@@ -333,8 +415,11 @@ __device__ __forceinline__ float edge_max(f3 r, float x0, float x1, float y0, fl
 }
 
 // One wave per work item (triangle, 32x32 tile of its box): 64 lanes, 2 rows per step.
+// MASK: the wave's triangle, and so its material, is wave-uniform; its id goes through readfirstlane and load_mask<true>
+// keeps the record on the scalar path. An unflagged triangle pays that one uniform branch, nothing per pixel.
+template <bool MASK, typename... M>
 __global__ __launch_bounds__(kWorkgroup) void raster_big(const uint32_t* __restrict__ idx, Workspace ws, RasterParams p,
-                                                  void* target, size_t pitch) {
+                                                  void* target, size_t pitch, M... mask) {
     const unsigned long long c = *ws.counter;
     const uint32_t n_entries = (uint32_t)(c >> ENTRY_SHIFT), count = (uint32_t)(c & ((1ull << ENTRY_SHIFT) - 1));
     const int lane = threadIdx.x & 63;
@@ -354,6 +439,8 @@ __global__ __launch_bounds__(kWorkgroup) void raster_big(const uint32_t* __restr
     uint2 e = ws.entries[e_idx];
     uint32_t next_first = e_idx + 1 < n_entries ? ws.entries[e_idx + 1].y : 0xFFFFFFFFu;
     TriSetup t = load_tri(ws, idx, (int)e.x, p);
+    MaskTri mk{};
+    if (MASK) mk = load_mask<true>(mask_of(mask...), idx, (int)__builtin_amdgcn_readfirstlane(e.x));
     for (uint32_t it = begin; it < end; ++it) {
         if (it >= next_first) {
             do {
@@ -362,6 +449,7 @@ __global__ __launch_bounds__(kWorkgroup) void raster_big(const uint32_t* __restr
                 next_first = e_idx + 1 < n_entries ? ws.entries[e_idx + 1].y : 0xFFFFFFFFu;
             } while (it >= next_first);
             t = load_tri(ws, idx, (int)e.x, p);
+            if (MASK) mk = load_mask<true>(mask_of(mask...), idx, (int)__builtin_amdgcn_readfirstlane(e.x));
         }
         const uint2 item = uint2{e.x, it - e.y};
         const int tiles_x = (t.px1 - t.px0 + TILE) / TILE;
@@ -375,7 +463,7 @@ __global__ __launch_bounds__(kWorkgroup) void raster_big(const uint32_t* __restr
 #if SOC_RASTER_FIXED_COLS
         const int x = x0 + (lane % TILE);
         if (x > x1) continue;
-        for (int y = y0 + lane / TILE; y <= y1; y += 64 / TILE) shade(t, (int)item.x, x, y, p, target, pitch);
+        for (int y = y0 + lane / TILE; y <= y1; y += 64 / TILE) shade<MASK>(t, (int)item.x, x, y, p, target, pitch, mk);
 #else
         // the wave's lanes as cols x (64 / cols) pixels, cols the smallest power of two >= the item's width (4..TILE):
         // a narrow box (the median large triangle's is 14 x 15 pixels at 4K) keeps most lanes on its pixels
@@ -383,7 +471,7 @@ __global__ __launch_bounds__(kWorkgroup) void raster_big(const uint32_t* __restr
         const int lc = cw <= 4 ? 2 : cw <= 8 ? 3 : cw <= 16 ? 4 : 5;   // log2 cols (TILE = 32)
         const int x = x0 + (lane & ((1 << lc) - 1));
         if (x > x1) continue;
-        for (int y = y0 + (lane >> lc); y <= y1; y += 64 >> lc) shade(t, (int)item.x, x, y, p, target, pitch);
+        for (int y = y0 + (lane >> lc); y <= y1; y += 64 >> lc) shade<MASK>(t, (int)item.x, x, y, p, target, pitch, mk);
 #endif
     }
 }
@@ -894,10 +982,21 @@ RasterSource draws_source(const soc_draw_scene* sc, const DrawTotals& tot, int v
     return RasterSource{sc->positions, nullptr, dw.indices, (int)tot.slots, (int)tot.triangles, dw.view[view], dw.slots, sc->transforms};
 }
 
+// The alpha test's table for each source: the mesh's own uvs and per-triangle materials, or the built scene's slot uvs and
+// its per-triangle material table.
+MaskTable mesh_mask(const soc_mesh* m, const soc_material* d_materials, int32_t material_count) {
+    return MaskTable{m->uvs, m->materials, d_materials, material_count};
+}
+MaskTable draws_mask(const soc_draw_scene* sc, const DrawTotals& tot, const soc_material* d_materials, int32_t material_count) {
+    const DrawWorkspace dw = draw_carve(sc->workspace, tot.slots, tot.triangles, sc->draw_count);
+    return MaskTable{reinterpret_cast<const float*>(dw.slot_uvs), dw.materials, d_materials, material_count};
+}
+
 // The vertex kernel, raster_small and raster_big into a W x H target: the visibility buffer (bias null) or, depth-only, a
 // D32 image with the Vulkan depth bias {constant, slope}.
+// mask: the MASK forms of the two triangle kernels with this table (null: the forms every unmasked call launches).
 int issue_raster(const RasterSource& src, const float* vp, int cull, void* target, size_t pitch, int W, int H, const float* bias,
-                 hipStream_t s, const char* pass) {
+                 hipStream_t s, const char* pass, const MaskTable* mask = nullptr) {
     // model, vp, width, height, vertex_count, triangle_count, cull, depth_only, bias_constant, bias_slope, small_pixels
     const RasterParams p{src.model ? mat4(src.model) : Mat4{}, mat4(vp), W, H, src.V, src.T, cull, bias ? 1 : 0,
                          bias ? bias[0] : 0.0f, bias ? bias[1] : 0.0f, SMALL_PIXELS};
@@ -905,9 +1004,14 @@ int issue_raster(const RasterSource& src, const float* vp, int cull, void* targe
     const unsigned blocks = ceil_div(max(src.V, 1), 256);
     if (!src.slots) launch("raster_setup", kWorkgroup, raster_setup, blocks, kWorkgroup, 0, s, src.positions, ws, p);
     else launch("raster_setup_draws", kWorkgroup, raster_setup_draws, blocks, kWorkgroup, 0, s, src.positions, src.slots, src.transforms, ws, p);
-    if (src.T > 0) {
-        launch("raster_small", kWorkgroup, raster_small, ceil_div(src.T, 256), kWorkgroup, 0, s, src.indices, ws, p, target, pitch);
-        launch("raster_big", kWorkgroup, raster_big, 2048, kWorkgroup, 0, s, src.indices, ws, p, target, pitch);
+    if (src.T > 0 && !mask) {
+        launch("raster_small", kWorkgroup, raster_small<false>, ceil_div(src.T, 256), kWorkgroup, 0, s, src.indices, ws, p, target, pitch);
+        launch("raster_big", kWorkgroup, raster_big<false>, 2048, kWorkgroup, 0, s, src.indices, ws, p, target, pitch);
+    } else if (src.T > 0) {
+        launch("raster_small_masked", kWorkgroup, raster_small<true, MaskTable>, ceil_div(src.T, 256), kWorkgroup, 0, s, src.indices,
+               ws, p, target, pitch, *mask);
+        launch("raster_big_masked", kWorkgroup, raster_big<true, MaskTable>, 2048, kWorkgroup, 0, s, src.indices, ws, p, target,
+               pitch, *mask);
     }
     return check_launch(pass);
 }
@@ -993,31 +1097,61 @@ int issue_resolve(const char* pass, const VertexStage& vs, const soc_mesh& mesh,
 
 using namespace soc;
 
-extern "C" int soc_raster_visibility(const soc_mesh* mesh, const float view_projection[16], int32_t cull,
-                                     uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
-                                     void* workspace, soc_stream stream) {
-    int rc = check_mesh(mesh, "soc_raster_visibility", false);
+// soc_raster_visibility / _depth and their _masked twins (masked: with the table's checks, then the MASK kernels)
+static int mesh_visibility(const char* name, const char* pass, const soc_mesh* mesh, const float* view_projection, int32_t cull,
+                           uint64_t* visibility, int32_t width, int32_t height, int32_t clear, void* workspace, bool masked,
+                           const soc_material* d_materials, int32_t material_count, soc_stream stream) {
+    int rc = check_mesh(mesh, name, false);
     if (rc) return rc;
     if (!view_projection || !visibility || !workspace || width <= 0 || height <= 0 || cull < 0 || cull > 2)
-        return set_error(SOC_E_INVALID_ARG, "soc_raster_visibility: null argument, bad extent or cull mode");
+        return set_error(SOC_E_INVALID_ARG, "%s: null argument, bad extent or cull mode", name);
+    if (masked && (rc = check_mask_table(d_materials, material_count, mesh->uvs, 0, name))) return rc;
+    const MaskTable mask = masked ? mesh_mask(mesh, d_materials, material_count) : MaskTable{};
     hipStream_t s = hs(stream);
     if (clear) clear_visibility(visibility, width, height, s);
     return issue_raster(mesh_source(mesh, workspace), view_projection, cull, visibility, (size_t)width * 8, width, height, nullptr,
-                        s, "raster_visibility");
+                        s, pass, masked ? &mask : nullptr);
 }
-
-extern "C" int soc_raster_depth(const soc_mesh* mesh, const float view_projection[16], int32_t cull, float bias_constant,
-                                float bias_slope, soc_img depth, void* workspace, soc_stream stream) {
-    int rc = check_mesh(mesh, "soc_raster_depth", false);
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "soc_raster_depth", "depth");
+static int mesh_depth(const char* name, const char* pass, const soc_mesh* mesh, const float* view_projection, int32_t cull,
+                      float bias_constant, float bias_slope, soc_img depth, void* workspace, bool masked,
+                      const soc_material* d_materials, int32_t material_count, soc_stream stream) {
+    int rc = check_mesh(mesh, name, false);
+    if (!rc) rc = check_img(depth, SOC_FMT_D32F, name, "depth");
     if (rc) return rc;
     if (!view_projection || !workspace || cull < 0 || cull > 2)
-        return set_error(SOC_E_INVALID_ARG, "soc_raster_depth: null argument or bad cull mode");
+        return set_error(SOC_E_INVALID_ARG, "%s: null argument or bad cull mode", name);
+    if (masked && (rc = check_mask_table(d_materials, material_count, mesh->uvs, 0, name))) return rc;
+    const MaskTable mask = masked ? mesh_mask(mesh, d_materials, material_count) : MaskTable{};
     hipStream_t s = hs(stream);
     clear_depth(depth, s);
     const float bias[2] = {bias_constant, bias_slope};
     return issue_raster(mesh_source(mesh, workspace), view_projection, cull, depth.data, (size_t)depth.pitch_bytes, depth.width,
-                        depth.height, bias, s, "raster_depth");
+                        depth.height, bias, s, pass, masked ? &mask : nullptr);
+}
+
+extern "C" int soc_raster_visibility(const soc_mesh* mesh, const float view_projection[16], int32_t cull,
+                                     uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
+                                     void* workspace, soc_stream stream) {
+    return mesh_visibility("soc_raster_visibility", "raster_visibility", mesh, view_projection, cull, visibility, width, height,
+                           clear, workspace, false, nullptr, 0, stream);
+}
+extern "C" int soc_raster_visibility_masked(const soc_mesh* mesh, const float view_projection[16], int32_t cull,
+                                            uint64_t* visibility, int32_t width, int32_t height, int32_t clear, void* workspace,
+                                            const soc_material* d_materials, int32_t material_count, soc_stream stream) {
+    return mesh_visibility("soc_raster_visibility_masked", "raster_visibility_masked", mesh, view_projection, cull, visibility,
+                           width, height, clear, workspace, true, d_materials, material_count, stream);
+}
+
+extern "C" int soc_raster_depth(const soc_mesh* mesh, const float view_projection[16], int32_t cull, float bias_constant,
+                                float bias_slope, soc_img depth, void* workspace, soc_stream stream) {
+    return mesh_depth("soc_raster_depth", "raster_depth", mesh, view_projection, cull, bias_constant, bias_slope, depth, workspace,
+                      false, nullptr, 0, stream);
+}
+extern "C" int soc_raster_depth_masked(const soc_mesh* mesh, const float view_projection[16], int32_t cull, float bias_constant,
+                                       float bias_slope, soc_img depth, void* workspace, const soc_material* d_materials,
+                                       int32_t material_count, soc_stream stream) {
+    return mesh_depth("soc_raster_depth_masked", "raster_depth_masked", mesh, view_projection, cull, bias_constant, bias_slope,
+                      depth, workspace, true, d_materials, material_count, stream);
 }
 
 extern "C" int soc_gbuffer_resolve(const soc_globals* g, const soc_mesh* mesh, const soc_material* d_materials,
@@ -1124,33 +1258,66 @@ extern "C" int soc_draw_scene_build(const soc_draw_scene* scene, soc_stream stre
     return SOC_OK;
 }
 
-extern "C" int soc_raster_visibility_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
-                                           uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
-                                           soc_stream stream) {
+static int draws_visibility(const char* name, const char* pass, const soc_draw_scene* scene, const float* view_projection,
+                            int32_t cull, uint64_t* visibility, int32_t width, int32_t height, int32_t clear, bool masked,
+                            const soc_material* d_materials, int32_t material_count, soc_stream stream) {
     DrawTotals tot;
-    int rc = check_built_scene(scene, "soc_raster_visibility_draws", false, tot);
+    // a masked call: the scene's description and the table first, so that every refusal that needs no build record comes
+    // before the one that does
+    int rc = masked ? check_draw_scene(scene, name, false, tot) : (int)SOC_OK;
+    if (!rc && masked) rc = check_mask_table(d_materials, material_count, scene->uvs, scene->material_count, name);
+    if (!rc) rc = check_built_scene(scene, name, false, tot);
     if (rc) return rc;
     if (!view_projection || !visibility || width <= 0 || height <= 0 || cull < 0 || cull > 2)
-        return set_error(SOC_E_INVALID_ARG, "soc_raster_visibility_draws: null argument, bad extent or cull mode");
+        return set_error(SOC_E_INVALID_ARG, "%s: null argument, bad extent or cull mode", name);
+    const MaskTable mask = masked ? draws_mask(scene, tot, d_materials, material_count) : MaskTable{};
     hipStream_t s = hs(stream);
     if (clear) clear_visibility(visibility, width, height, s);
     return issue_raster(draws_source(scene, tot, 0), view_projection, cull, visibility, (size_t)width * 8, width, height, nullptr, s,
-                        "raster_visibility_draws");
+                        pass, masked ? &mask : nullptr);
 }
-
-extern "C" int soc_raster_depth_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
-                                      float bias_constant, float bias_slope, soc_img depth, soc_stream stream) {
+static int draws_depth(const char* name, const char* pass, const soc_draw_scene* scene, const float* view_projection, int32_t cull,
+                       float bias_constant, float bias_slope, soc_img depth, bool masked, const soc_material* d_materials,
+                       int32_t material_count, soc_stream stream) {
     DrawTotals tot;
-    int rc = check_built_scene(scene, "soc_raster_depth_draws", false, tot);
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "soc_raster_depth_draws", "depth");
+    int rc = masked ? check_draw_scene(scene, name, false, tot) : (int)SOC_OK;   // the order: see draws_visibility
+    if (!rc && masked) rc = check_mask_table(d_materials, material_count, scene->uvs, scene->material_count, name);
+    if (!rc) rc = check_built_scene(scene, name, false, tot);
+    if (!rc) rc = check_img(depth, SOC_FMT_D32F, name, "depth");
     if (rc) return rc;
     if (!view_projection || cull < 0 || cull > 2)
-        return set_error(SOC_E_INVALID_ARG, "soc_raster_depth_draws: null argument or bad cull mode");
+        return set_error(SOC_E_INVALID_ARG, "%s: null argument or bad cull mode", name);
+    const MaskTable mask = masked ? draws_mask(scene, tot, d_materials, material_count) : MaskTable{};
     hipStream_t s = hs(stream);
     clear_depth(depth, s);
     const float bias[2] = {bias_constant, bias_slope};
     return issue_raster(draws_source(scene, tot, 1), view_projection, cull, depth.data, (size_t)depth.pitch_bytes, depth.width,
-                        depth.height, bias, s, "raster_depth_draws");
+                        depth.height, bias, s, pass, masked ? &mask : nullptr);
+}
+
+extern "C" int soc_raster_visibility_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                           uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
+                                           soc_stream stream) {
+    return draws_visibility("soc_raster_visibility_draws", "raster_visibility_draws", scene, view_projection, cull, visibility,
+                            width, height, clear, false, nullptr, 0, stream);
+}
+extern "C" int soc_raster_visibility_draws_masked(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                                  uint64_t* visibility, int32_t width, int32_t height, int32_t clear,
+                                                  const soc_material* d_materials, int32_t material_count, soc_stream stream) {
+    return draws_visibility("soc_raster_visibility_draws_masked", "raster_visibility_draws_masked", scene, view_projection, cull,
+                            visibility, width, height, clear, true, d_materials, material_count, stream);
+}
+
+extern "C" int soc_raster_depth_draws(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                      float bias_constant, float bias_slope, soc_img depth, soc_stream stream) {
+    return draws_depth("soc_raster_depth_draws", "raster_depth_draws", scene, view_projection, cull, bias_constant, bias_slope,
+                       depth, false, nullptr, 0, stream);
+}
+extern "C" int soc_raster_depth_draws_masked(const soc_draw_scene* scene, const float view_projection[16], int32_t cull,
+                                             float bias_constant, float bias_slope, soc_img depth,
+                                             const soc_material* d_materials, int32_t material_count, soc_stream stream) {
+    return draws_depth("soc_raster_depth_draws_masked", "raster_depth_draws_masked", scene, view_projection, cull, bias_constant,
+                       bias_slope, depth, true, d_materials, material_count, stream);
 }
 
 // soc_gbuffer_resolve_draws (previous null) and soc_gbuffer_resolve_draws_motion: the same checks, tables and resolve; the

@@ -66,6 +66,17 @@ int check_mesh(const soc_mesh* mesh, const char* pass, bool attributes) {
     return SOC_OK;
 }
 
+int check_mask_table(const soc_material* d_materials, int32_t material_count, const float* uvs, int32_t scene_materials,
+                     const char* pass) {
+    if (!d_materials || material_count <= 0)
+        return set_error(SOC_E_INVALID_ARG, "%s: null materials or material_count %d <= 0", pass, material_count);
+    if (!uvs) return set_error(SOC_E_INVALID_ARG, "%s: the alpha test needs uvs", pass);
+    if (material_count < scene_materials)
+        return set_error(SOC_E_INVALID_ARG, "%s: %d materials, the scene's draws name up to %d", pass, material_count,
+                         scene_materials);
+    return SOC_OK;
+}
+
 bool draw_totals(const soc_draw* draws, int32_t draw_count, DrawTotals& t) {
     if (draw_count < 0 || (draw_count > 0 && !draws)) return false;
     for (int32_t d = 0; d < draw_count; ++d) {

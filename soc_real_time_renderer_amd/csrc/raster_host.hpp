@@ -24,6 +24,11 @@ constexpr uint32_t DRAWS_OK = 0xFFFFFFFFu;
 
 int check_mesh(const soc_mesh* mesh, const char* pass, bool attributes);
 
+// What a *_masked call adds to its twin's checks: the material table, the uvs the alpha test interpolates and, for a
+// draw scene, a table that covers every draw's material (scene_materials; 0 for a mesh).
+int check_mask_table(const soc_material* d_materials, int32_t material_count, const float* uvs, int32_t scene_materials,
+                     const char* pass);
+
 struct DrawTotals { long long slots = 0, triangles = 0; };
 // Slot and triangle totals of a draw list; false on a null list, a negative count or field, or totals beyond int32.
 bool draw_totals(const soc_draw* draws, int32_t draw_count, DrawTotals& t);

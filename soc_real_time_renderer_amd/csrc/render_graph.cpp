@@ -56,6 +56,14 @@ void build_raster_passes(soc_renderer* r) {
     add_pass(r, "DepthPrepass", "Depth Prepass", pre, 0, res_mask({SOC_RES_VISIBILITY}),
              [r](const soc_globals* g, hipStream_t s) {
                  const soc_img& d = r->img.depth;
+                 const float* pv = g->camera_projection_view_matrix;
+                 const soc_raster_scene& sc = r->scene;
+                 if (r->alpha_mask)   // soc_renderer_set_alpha_mask: the masked twins with the head's material table
+                     return r->has_draws
+                         ? soc_raster_visibility_draws_masked(&r->draw_scene, pv, SOC_CULL_FRONT, sc.visibility, d.width, d.height, 1,
+                                                              sc.materials, sc.material_count, (soc_stream)s)
+                         : soc_raster_visibility_masked(&sc.mesh, pv, SOC_CULL_FRONT, sc.visibility, d.width, d.height, 1,
+                                                        sc.workspace, sc.materials, sc.material_count, (soc_stream)s);
                  if (r->has_draws)
                      return soc_raster_visibility_draws(&r->draw_scene, g->camera_projection_view_matrix, SOC_CULL_FRONT,
                                                         r->scene.visibility, d.width, d.height, 1, (soc_stream)s);
@@ -69,23 +77,28 @@ void build_raster_passes(soc_renderer* r) {
     if (r->scene.shadow)
         add_pass(r, "SunShadowDraw", "Shadows", pre, 0, res_mask({SOC_RES_SUN_SHADOW}),
                  [r, shadow_lane](const soc_globals* g, hipStream_t s) {
+                     // one shadow draw into `target` with the pipeline's cull and bias: the head's call, or with
+                     // soc_renderer_set_alpha_mask its masked twin with the head's material table
+                     auto draw = [r, shadow_lane, s](const float* pv, soc_img target) {
+                         const soc_raster_scene& sc = r->scene;
+                         void* ws = shadow_lane ? r->shadow_ws : sc.workspace;
+                         if (r->alpha_mask)
+                             return r->has_draws
+                                 ? soc_raster_depth_draws_masked(&r->draw_scene, pv, SOC_CULL_BACK, 1.25f, 1.75f, target, sc.materials,
+                                                                 sc.material_count, (soc_stream)s)
+                                 : soc_raster_depth_masked(&sc.mesh, pv, SOC_CULL_BACK, 1.25f, 1.75f, target, ws, sc.materials,
+                                                           sc.material_count, (soc_stream)s);
+                         return r->has_draws ? soc_raster_depth_draws(&r->draw_scene, pv, SOC_CULL_BACK, 1.25f, 1.75f, target, (soc_stream)s)
+                                             : soc_raster_depth(&sc.mesh, pv, SOC_CULL_BACK, 1.25f, 1.75f, target, ws, (soc_stream)s);
+                     };
                      if (r->has_cascades) {   // every cascade into its slab of the atlas, same cull and bias
                          for (int k = 0; k < r->cascades.count; ++k) {
-                             const float* pv = r->cascades.projection_view[k];
-                             const int rc = r->has_draws
-                                 ? soc_raster_depth_draws(&r->draw_scene, pv, SOC_CULL_BACK, 1.25f, 1.75f, r->cascade_slab(k), (soc_stream)s)
-                                 : soc_raster_depth(&r->scene.mesh, pv, SOC_CULL_BACK, 1.25f, 1.75f, r->cascade_slab(k),
-                                                    shadow_lane ? r->shadow_ws : r->scene.workspace, (soc_stream)s);
+                             const int rc = draw(r->cascades.projection_view[k], r->cascade_slab(k));
                              if (rc) return rc;
                          }
                          return (int)SOC_OK;
                      }
-                     if (r->has_draws)
-                         return soc_raster_depth_draws(&r->draw_scene, g->sun_info.projection_view_matrix, SOC_CULL_BACK,
-                                                       1.25f, 1.75f, r->img.shadow, (soc_stream)s);
-                     return soc_raster_depth(&r->scene.mesh, g->sun_info.projection_view_matrix, SOC_CULL_BACK, 1.25f,
-                                             1.75f, r->img.shadow, shadow_lane ? r->shadow_ws : r->scene.workspace,
-                                             (soc_stream)s);
+                     return draw(g->sun_info.projection_view_matrix, r->img.shadow);
                  }, shadow_lane ? SOC_PASS_ASYNC : 0);
     // SunShadowDrawTerrainTask (renderer.cpp:983-990, sun_shadow_draw_terrain.inl): loads the shadow image SunShadowDraw
     // wrote and draws the terrain into it unbiased, on that pass's lane behind it (the layer's shadow workspace is its
@@ -842,4 +855,10 @@ extern "C" const char* soc_renderer_pass_name(const soc_renderer* r, int32_t i) 
 extern "C" const char* soc_renderer_pass_group(const soc_renderer* r, int32_t i) {
     if (!r || i < 0 || i >= (int32_t)r->passes.size()) return nullptr;
     return r->passes[i].group.c_str();
+}
+
+extern "C" int soc_renderer_set_alpha_mask(soc_renderer* r, int32_t enable) {
+    if (!r) return set_error(SOC_E_INVALID_ARG, "soc_renderer_set_alpha_mask: null renderer");
+    r->alpha_mask = enable != 0;   // read by DepthPrepass and SunShadowDraw when a frame runs: nothing is rebuilt
+    return SOC_OK;
 }

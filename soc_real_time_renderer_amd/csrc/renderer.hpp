@@ -102,6 +102,9 @@ struct soc_renderer {
     // soc_renderer_set_light_bounds: Composition launches the bounded kernels on this device record (null: unbounded)
     const void* light_bounds = nullptr;
     uint32_t light_flags = 0;
+    // soc_renderer_set_alpha_mask: DepthPrepass and SunShadowDraw call the *_masked raster twins with the head's
+    // material table (read when a frame runs: no pass is rebuilt, and the flag survives a change of head)
+    bool alpha_mask = false;
     // soc_renderer_set_sun_cascades: a copy of the record; img.shadow is then its atlas, the shadow passes draw every
     // cascade into its slab and Composition launches the cascaded call
     soc_sun_cascades cascades{};

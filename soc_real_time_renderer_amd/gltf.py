@@ -52,7 +52,10 @@ def load_image(path: str, max_size: Optional[int] = None) -> np.ndarray:
 
 def load(path: str, max_texture: Optional[int] = None, images: Optional[dict] = None) -> dict:
     """Mesh arrays (positions, normals, uvs: float32; indices (T, 3) and materials (T,): uint32) and
-    `materials`: a list of dicts {albedo, emissive (RGBA8 arrays or None), albedo_srgb, emissive_srgb}.
+    `materials`: a list of dicts {albedo, emissive (RGBA8 arrays or None), albedo_srgb, emissive_srgb, alpha_mode (the
+    document's alphaMode, default "OPAQUE"), alpha_cutoff (default 0.5), base_color_factor (default four ones)}. The alpha
+    channel of the albedo is kept. "MASK" feeds raster.material(alpha_mode="MASK", alpha_cutoff=..., albedo_factor=...);
+    "BLEND" is reported as it stands and rendered opaque: a deferred frame holds one surface per pixel.
     `images` may map image uri -> RGBA8 array to bypass decoding."""
     base = os.path.dirname(os.path.abspath(path))
     with open(path) as f:
@@ -100,9 +103,12 @@ def load(path: str, max_texture: Optional[int] = None, images: Optional[dict] = 
             # normalTexture: UNORM (model.cpp:52-71 makes only baseColor / emissive images sRGB), :217-224
             "normal": tex(m["normalTexture"]["index"]) if "normalTexture" in m else None,
             "albedo_srgb": True, "emissive_srgb": True,
+            "alpha_mode": str(m.get("alphaMode", "OPAQUE")), "alpha_cutoff": float(m.get("alphaCutoff", 0.5)),
+            "base_color_factor": tuple(float(v) for v in pbr.get("baseColorFactor", (1.0, 1.0, 1.0, 1.0))),
         })
     if not materials:
-        materials.append({"albedo": None, "emissive": None, "normal": None, "albedo_srgb": True, "emissive_srgb": True})
+        materials.append({"albedo": None, "emissive": None, "normal": None, "albedo_srgb": True, "emissive_srgb": True,
+                          "alpha_mode": "OPAQUE", "alpha_cutoff": 0.5, "base_color_factor": (1.0, 1.0, 1.0, 1.0)})
     return {"positions": np.ascontiguousarray(np.concatenate(pos)), "normals": np.ascontiguousarray(np.concatenate(nrm)),
             "uvs": np.ascontiguousarray(np.concatenate(uv)), "indices": np.ascontiguousarray(np.concatenate(idx)),
             "materials": np.ascontiguousarray(np.concatenate(mat)), "material_list": materials, "vertex_count": total}

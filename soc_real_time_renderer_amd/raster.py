@@ -16,11 +16,11 @@ import numpy as np
 import torch
 
 from . import _abi, _check, _gp, _ptr, _stream, img, lib
-from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, MATERIAL_MIPMAPPED,
+from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, FMT_RGBA8_SRGB, FMT_RGBA8_UNORM, MATERIAL_ALPHA_MASK, MATERIAL_MIPMAPPED,
                    MATERIAL_NORMAL_MAP, MATERIAL_NORMAL_TEXTURE, MATERIAL_PAIRED_TEXELS, MATERIAL_ZERO_VELOCITY, Material, Mesh,
                    SocImg)
 
-__all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "sun_shadow_draw_cascades", "MATERIAL_ZERO_VELOCITY", "MeshBuffers", "MipTexture", "material",
+__all__ = ["CULL_NONE", "CULL_FRONT", "CULL_BACK", "sun_shadow_draw_cascades", "MATERIAL_ZERO_VELOCITY", "MATERIAL_ALPHA_MASK", "MeshBuffers", "MipTexture", "material",
            "normal_matrix", "materials_device", "raster_visibility", "raster_depth", "gbuffer_resolve",
            "SHADOW_BIAS_CONSTANT", "SHADOW_BIAS_SLOPE", "DrawScene", "draw", "transforms_device", "update_transforms",
            "raster_visibility_draws", "raster_depth_draws", "gbuffer_resolve_draws",
@@ -135,13 +135,20 @@ class MipTexture:
 
 def material(albedo=None, emissive=None, albedo_factor=(1.0, 1.0, 1.0, 1.0), emissive_factor=(1.0, 1.0, 1.0, 1.0),
              flags=0, has_emissive: Optional[bool] = None, srgb=True, normal_map=None, normal_texture=None,
-             max_anisotropy: float = 16.0) -> Material:
+             max_anisotropy: float = 16.0, alpha_mode: str = "OPAQUE", alpha_cutoff: float = 0.5) -> Material:
     """soc_material: albedo / emissive RGBA8 textures ((H, W, 4) uint8 tensors or arrays; sRGB like the
     reference's baseColor/emissive images, model.cpp:52-71) or None (white / no emissive); normal_texture: the
     glTF tangent-space normal image (RGBA8 UNORM, has_normal_image, g_buffer_generation.inl:197-211).
     MipTexture arguments make the material mip-mapped (SOC_MATERIAL_MIPMAPPED: trilinear, anisotropy up to
-    max_anisotropy as the reference's sampler, texture.cpp:121-136); then every texture given must be one."""
+    max_anisotropy as the reference's sampler, texture.cpp:121-136); then every texture given must be one.
+    alpha_mode "MASK" (glTF alphaMode) makes it a cutout material: SOC_MATERIAL_ALPHA_MASK and alpha_cutoff, read by the
+    masked raster calls only (materials= below), which test level 0 of the albedo's alpha times albedo_factor[3]."""
+    if alpha_mode not in ("OPAQUE", "MASK"):
+        raise ValueError(f"alpha_mode {alpha_mode!r}: \"OPAQUE\" or \"MASK\" (a deferred frame has no place for BLEND)")
     m = Material()
+    if alpha_mode == "MASK":
+        m.flags |= MATERIAL_ALPHA_MASK
+        m.alpha_cutoff = float(alpha_cutoff)
     fmt = FMT_RGBA8_SRGB if srgb else None
     given = [t for t in (albedo, emissive, normal_texture) if t is not None]
     mipped = any(isinstance(t, MipTexture) for t in given)
@@ -201,32 +208,52 @@ def materials_device(mats: Sequence[Material], device="cuda") -> torch.Tensor:
     return torch.from_numpy(raw).to(device)
 
 
+def _mask_args(materials, material_count):
+    """The two extra arguments of a *_masked call: the device material table and its length (the table's own when
+    material_count is None)."""
+    n = materials.numel() // C.sizeof(Material) if material_count is None else material_count
+    return _ptr(materials), int(n)
+
+
 def raster_visibility(mesh: MeshBuffers, view_projection, cull, visibility: torch.Tensor, workspace: torch.Tensor,
-                      clear=True, stream=None):
-    """Depth prepass into an (H, W) int64/uint64 visibility buffer (depth bits << 32 | triangle key)."""
+                      clear=True, stream=None, materials=None, material_count=None):
+    """Depth prepass into an (H, W) int64/uint64 visibility buffer (depth bits << 32 | triangle key). materials (a
+    materials_device table): soc_raster_visibility_masked, the alpha test on triangles of MASK materials."""
     H, W = visibility.shape
     vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    if materials is not None:
+        _check(lib().soc_raster_visibility_masked(C.byref(mesh.struct), vp, int(cull), _ptr(visibility), W, H,
+                                                  int(bool(clear)), _ptr(workspace), *_mask_args(materials, material_count),
+                                                  _stream(stream)), "raster_visibility_masked")
+        return
     _check(lib().soc_raster_visibility(C.byref(mesh.struct), vp, int(cull), _ptr(visibility), W, H, int(bool(clear)),
                                        _ptr(workspace), _stream(stream)), "raster_visibility")
 
 
 def raster_depth(mesh: MeshBuffers, view_projection, cull, depth: torch.Tensor, workspace: torch.Tensor,
-                 bias_constant=0.0, bias_slope=0.0, stream=None):
-    """Depth-only raster into a D32 image (the sun shadow map with SHADOW_BIAS_*)."""
+                 bias_constant=0.0, bias_slope=0.0, stream=None, materials=None, material_count=None):
+    """Depth-only raster into a D32 image (the sun shadow map with SHADOW_BIAS_*). materials: soc_raster_depth_masked."""
     vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    if materials is not None:
+        _check(lib().soc_raster_depth_masked(C.byref(mesh.struct), vp, int(cull), float(bias_constant), float(bias_slope),
+                                             img(depth), _ptr(workspace), *_mask_args(materials, material_count),
+                                             _stream(stream)), "raster_depth_masked")
+        return
     _check(lib().soc_raster_depth(C.byref(mesh.struct), vp, int(cull), float(bias_constant), float(bias_slope),
                                   img(depth), _ptr(workspace), _stream(stream)), "raster_depth")
 
 
-def sun_shadow_draw_cascades(mesh: MeshBuffers, record, atlas: torch.Tensor, workspace: torch.Tensor, stream=None):
+def sun_shadow_draw_cascades(mesh: MeshBuffers, record, atlas: torch.Tensor, workspace: torch.Tensor, stream=None,
+                             materials=None, material_count=None):
     """SunShadowDraw of every cascade of a soc_sun_cascades record into its slab of the atlas (rows [k S, (k + 1) S)):
-    raster_depth per slab with projection_view[k], cull BACK and the reference's shadow bias."""
+    raster_depth per slab with projection_view[k], cull BACK and the reference's shadow bias (materials: the masked
+    call per slab, cutout casters)."""
     S = int(record.map_size)
     if tuple(atlas.shape) != (int(record.count) * S, S):
         raise ValueError(f"atlas {tuple(atlas.shape)} is not ({int(record.count) * S}, {S})")
     for k in range(int(record.count)):
         raster_depth(mesh, list(record.projection_view[k]), CULL_BACK, atlas[k * S:(k + 1) * S], workspace,
-                     bias_constant=1.25, bias_slope=1.75, stream=stream)
+                     bias_constant=1.25, bias_slope=1.75, stream=stream, materials=materials, material_count=material_count)
 
 
 def gbuffer_resolve(g, mesh: MeshBuffers, d_materials: torch.Tensor, material_count: int, visibility: torch.Tensor,
@@ -338,18 +365,29 @@ class DrawScene:
             pass
 
 
-def raster_visibility_draws(scene: DrawScene, view_projection, cull, visibility: torch.Tensor, clear=True, stream=None):
-    """raster_visibility of a draw scene: global triangle ids in draw order."""
+def raster_visibility_draws(scene: DrawScene, view_projection, cull, visibility: torch.Tensor, clear=True, stream=None,
+                            materials=None, material_count=None):
+    """raster_visibility of a draw scene: global triangle ids in draw order (materials: the masked call)."""
     H, W = visibility.shape
     vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    if materials is not None:
+        _check(lib().soc_raster_visibility_draws_masked(C.byref(scene.struct), vp, int(cull), _ptr(visibility), W, H,
+                                                        int(bool(clear)), *_mask_args(materials, material_count),
+                                                        _stream(stream)), "raster_visibility_draws_masked")
+        return
     _check(lib().soc_raster_visibility_draws(C.byref(scene.struct), vp, int(cull), _ptr(visibility), W, H, int(bool(clear)),
                                              _stream(stream)), "raster_visibility_draws")
 
 
 def raster_depth_draws(scene: DrawScene, view_projection, cull, depth: torch.Tensor, bias_constant=0.0, bias_slope=0.0,
-                       stream=None):
-    """raster_depth of a draw scene (the sun shadow map with SHADOW_BIAS_*)."""
+                       stream=None, materials=None, material_count=None):
+    """raster_depth of a draw scene (the sun shadow map with SHADOW_BIAS_*; materials: the masked call)."""
     vp = (C.c_float * 16)(*[float(v) for v in np.asarray(view_projection, np.float32).reshape(16)])
+    if materials is not None:
+        _check(lib().soc_raster_depth_draws_masked(C.byref(scene.struct), vp, int(cull), float(bias_constant),
+                                                   float(bias_slope), img(depth), *_mask_args(materials, material_count),
+                                                   _stream(stream)), "raster_depth_draws_masked")
+        return
     _check(lib().soc_raster_depth_draws(C.byref(scene.struct), vp, int(cull), float(bias_constant), float(bias_slope),
                                         img(depth), _stream(stream)), "raster_depth_draws")
 

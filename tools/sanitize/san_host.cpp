@@ -531,6 +531,40 @@ void draw_scenes(const soc_globals& g) {
                SOC_E_INVALID_ARG && mentions("normals"), "per-frame: resolve without normals");
     soc_draw_scene_release(nullptr);
     soc_draw_scene_release(&unbuilt);   // an unknown workspace: no-op
+
+    // the alpha-mask twins (check_mask_table): every refusal of tests/test_alpha_mask_abi.py, all before any HIP call
+    soc_mesh mesh;
+    std::memset(&mesh, 0, sizeof mesh);
+    mesh.positions = mesh.normals = mesh.uvs = reinterpret_cast<const float*>(256);
+    mesh.indices = reinterpret_cast<const uint32_t*>(256);
+    mesh.vertex_count = 3;
+    mesh.triangle_count = 1;
+    void* ws = reinterpret_cast<void*>(4096);
+    for (int k = 0; k < 3; ++k) {
+        soc_mesh m = mesh;
+        if (k == 2) m.uvs = nullptr;
+        const soc_material* table = k == 0 ? nullptr : mats;
+        const int32_t count = k == 1 ? 0 : 2;
+        const char* word = k == 2 ? "uvs" : "materials";
+        expect(soc_raster_visibility_masked(&m, vp, 1, vis.data(), 64, 36, 1, ws, table, count, nullptr) == SOC_E_INVALID_ARG &&
+                   mentions("soc_raster_visibility_masked") && mentions(word), "masked visibility: table or uvs");
+        expect(soc_raster_depth_masked(&m, vp, 2, 1.25f, 1.75f, depth.img, ws, table, count, nullptr) == SOC_E_INVALID_ARG &&
+                   mentions("soc_raster_depth_masked") && mentions(word), "masked depth: table or uvs");
+        soc_draw_scene sc = make_scene(one);
+        if (k == 2) sc.uvs = nullptr;
+        expect(soc_raster_visibility_draws_masked(&sc, vp, 1, vis.data(), 64, 36, 1, table, count, nullptr) == SOC_E_INVALID_ARG &&
+                   mentions("soc_raster_visibility_draws_masked") && mentions(word), "masked visibility of draws: table or uvs");
+        expect(soc_raster_depth_draws_masked(&sc, vp, 2, 1.25f, 1.75f, depth.img, table, count, nullptr) == SOC_E_INVALID_ARG &&
+                   mentions("soc_raster_depth_draws_masked") && mentions(word), "masked depth of draws: table or uvs");
+    }
+    expect(soc_raster_visibility_draws_masked(&unbuilt, vp, 1, vis.data(), 64, 36, 1, mats, 1, nullptr) == SOC_E_INVALID_ARG &&
+               mentions("name up to 2"), "masked visibility of draws: fewer materials than the scene's");
+    expect(soc_raster_depth_draws_masked(&unbuilt, vp, 2, 1.25f, 1.75f, depth.img, mats, 2, nullptr) == SOC_E_INVALID_ARG &&
+               mentions("not built"), "masked depth of draws: never built");
+    expect(soc_raster_visibility_draws_masked(nullptr, vp, 1, vis.data(), 64, 36, 1, mats, 2, nullptr) == SOC_E_INVALID_ARG,
+           "masked visibility of draws: null scene");
+    expect(soc_renderer_set_alpha_mask(nullptr, 1) == SOC_E_INVALID_ARG && mentions("soc_renderer_set_alpha_mask"),
+           "set_alpha_mask: null renderer");
 }
 }  // namespace
 
