@@ -12,9 +12,8 @@
 #include <type_traits>
 
 #include "bloom_w.hpp"
+#include "composition_plan.hpp"
 #include "light_cull.hpp"
-#include "luminance.hpp"
-#include "soc_internal.hpp"
 
 // Profiling builds only (tools/kernel_variants.py): 1 = no shadow-map tap, 2 = no AO tap, 3 = neither.
 #ifndef SOC_COMP_PROFILE
@@ -23,23 +22,6 @@
 
 namespace soc {
 namespace {
-
-struct CompParams {
-    Mat4 inv_proj, inv_view, sun_pv;
-    Mat4 sun_clip;        // sun_pv * inv_view * inv_proj: NDC (x, y, depth, 1) -> sun clip space
-    float sun_dir[3], ambient[3], cam[3];
-    float ef, df, emissive_strength, ao_strength;
-    uint32_t npl, nsl;
-    int swz;   // XCD-aware tile order (fast path)
-    uint32_t* bins;        // fused histogram: 8 x 256 scratch copies (composition_pair<true>)
-    float lmin, lrange;    // log_min_luminance, log_max - log_min
-    BinFast bf;            // lum_bin_fast parameters
-    const soc_globals* __restrict__ dg;  // device globals (lights), may be null when npl == nsl == 0
-    int sky_external;      // 1: sky pixels (depth == 1) are written and binned by sky_compose_pair (second lane)
-    float rw, rh;          // recip_rn(target extent) for the pixel-centre uv (div_rn)
-    int bloom_zero_skip;   // SOC_BLOOM_ZERO_SKIP: the in-kernel bloom skips its sums on all-zero mip1 tiles (BL)
-    int bloom_sparse;      // SOC_BLOOM_SPARSE: the workgroup's cell is tested against mip3 (zero_cells, bloom_w.hpp)
-};
 
 __device__ __forceinline__ float fast_pow(float x, float y) {
     // pow(x, y) = exp2(y * log2(x)) on the native transcendental units (as the reference GPU does)
@@ -137,7 +119,6 @@ __device__ __forceinline__ T spec_exp_acos2(T c) {
 // the wave's light masks instead of 0 .. n: mask_of(0 / 1) the point lights 0-63 / 64-127 that may reach a lit pixel of
 // the wave, mask_of(2 / 3) the spot lights (composition_pair's cull; each is asked for just before its loop, so one mask
 // is live at a time). The index stays scalar, so the records still come through the scalar unit. *ran: lights run.
-constexpr int kLbBounded = 1, kLbCull = 2, kLbCount = 4;
 struct NoMasks {
     __device__ uint64_t operator()(int) const { return 0ull; }
 };
@@ -193,6 +174,13 @@ __device__ __forceinline__ V3<T> light_sum(const soc_globals* __restrict__ dg, u
         const T nh = acos_fast(c);
         return (diffuse + vexp2((nh * nh) * nlog2e)) * (inv * inv);
     };
+    // a spot light's cone term (:148-151): the angle to its axis between the outer and the inner cut-off
+    auto cone = [&](const soc_spot_light& L, const V3<T>& ld) {
+        const float sdx = -L.direction[0], sdy = -L.direction[1], sdz = -L.direction[2];
+        const float sk = __builtin_amdgcn_rsqf(__builtin_fmaf(sdz, sdz, __builtin_fmaf(sdy, sdy, sdx * sdx)));
+        const T theta = vfma(ld.z, bcv(sdz, z), vfma(ld.y, bcv(sdy, z), ld.x * bcv(sdx, z))) * bcv(sk, z);
+        return vclamp01(vdiv(theta - bcv(L.outer_cut_off, z), L.cut_off - L.outer_cut_off));
+    };
     auto add = [&](const float* col, T s) {
         acc = V3<T>{vfma(bcv(col[0], z), s, acc.x), vfma(bcv(col[1], z), s, acc.y), vfma(bcv(col[2], z), s, acc.z)};
     };
@@ -229,10 +217,7 @@ __device__ __forceinline__ V3<T> light_sum(const soc_globals* __restrict__ dg, u
             T inv;
             V3<T> ld;
             const T b = shade_light(L.position, inv, ld);
-            const float sdx = -L.direction[0], sdy = -L.direction[1], sdz = -L.direction[2];
-            const float sk = __builtin_amdgcn_rsqf(__builtin_fmaf(sdz, sdz, __builtin_fmaf(sdy, sdy, sdx * sdx)));
-            const T theta = vfma(ld.z, bcv(sdz, z), vfma(ld.y, bcv(sdy, z), ld.x * bcv(sdx, z))) * bcv(sk, z);
-            T f = vclamp01(vdiv(theta - bcv(L.outer_cut_off, z), L.cut_off - L.outer_cut_off));
+            T f = cone(L, ld);
             if (inv_r2 != 0.0f) f = window(inv_r2) * f;
             add_where(L.color, b * bcv(L.intensity, z) * f, f);
         };
@@ -269,10 +254,7 @@ __device__ __forceinline__ V3<T> light_sum(const soc_globals* __restrict__ dg, u
         T inv;
         V3<T> ld;
         const T b = shade_light(L.position, inv, ld);
-        const float sdx = -L.direction[0], sdy = -L.direction[1], sdz = -L.direction[2];
-        const float sk = __builtin_amdgcn_rsqf(__builtin_fmaf(sdz, sdz, __builtin_fmaf(sdy, sdy, sdx * sdx)));
-        const T theta = vfma(ld.z, bcv(sdz, z), vfma(ld.y, bcv(sdy, z), ld.x * bcv(sdx, z))) * bcv(sk, z);
-        const T intensity = vclamp01(vdiv(theta - bcv(L.outer_cut_off, z), L.cut_off - L.outer_cut_off));
+        const T intensity = cone(L, ld);
         add(L.color, b * bcv(L.intensity, z) * intensity);
     }
     return acc;
@@ -289,6 +271,14 @@ struct ShadePre {
     float occl;
     f3 em;
 };
+// shade_pre without the shadow: direct = dot(n, -sun), to be multiplied by the sun's shadow term (here, or cascade_shadow)
+__device__ __forceinline__ ShadePre shade_pre_unshadowed(const CompParams& p, f3 emissive, f3 n, float ssao) {
+    ShadePre s;
+    s.em = emissive * p.emissive_strength;
+    s.occl = fast_pow(ssao, p.ao_strength);
+    s.direct = fmaxf(0.0f, dot3(n, -mk3(p.sun_dir[0], p.sun_dir[1], p.sun_dir[2])));
+    return s;
+}
 template <typename ShadowImg = DImg>
 __device__ __forceinline__ ShadePre shade_pre(const CompParams& p, float u, float v, float d, f3 emissive, f3 n, float ssao,
                                               const ShadowImg& shadow) {
@@ -303,10 +293,8 @@ __device__ __forceinline__ ShadePre shade_pre(const CompParams& p, float u, floa
     float e = __expf(p.ef * (pcz - sd));
     if (p.df != 1.0f) e = fast_pow(e, p.df);   // pow(x, 1.0) == x exactly
     const float sun_shadow = clampf(e, 0.0f, 1.0f);
-    ShadePre s;
-    s.em = emissive * p.emissive_strength;
-    s.occl = fast_pow(ssao, p.ao_strength);
-    s.direct = fmaxf(0.0f, dot3(n, -mk3(p.sun_dir[0], p.sun_dir[1], p.sun_dir[2]))) * sun_shadow;
+    ShadePre s = shade_pre_unshadowed(p, emissive, n, ssao);
+    s.direct *= sun_shadow;
     return s;
 }
 // get_world_position_from_depth, :114-122
@@ -339,8 +327,6 @@ __device__ __forceinline__ f4 shade(const CompParams& p, float u, float v, float
     }
     return shade_post(p, s, albedo, nullptr);
 }
-
-constexpr int BX = 64, BY = 4;
 
 // Fast path: all full-res images share the target extent, width even, rows 16-B aligned.
 // HIST: GenerateLuminanceHistogramTask fused in (generate_luminance_histogram.inl:59-78): the bins of the
@@ -377,18 +363,11 @@ constexpr int BX = 64, BY = 4;
 // box's bounding sphere; an unlimited point light always passes), and the ballots, made provably wave-uniform, are the
 // masks the loops walk. A wave without a lit pixel has empty masks. kLbCount: the wave adds the number of lights its
 // loops run to *la.shaded (the measuring calls only: one same-address atomic per wave).
-struct LightArgs {
-    const LightBoundsDev* lb;
-    uint32_t* shaded;
-};
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
 }
-struct CompParamsBounded : CompParams {
-    LightArgs la;
-};
 // Cascaded sun shadows (CS; soc_composition_cascaded), in instantiations of their own with a parameter
 // block of their own: `shadow` is the atlas (S x count * S, cascade c = rows [c * S, (c + 1) * S)), pv[c] the cascade's
 // projection_view (world -> sun clip space), ef[c] its ESM factor, split[] the stored depths that separate the cascades
@@ -407,15 +386,6 @@ struct CompParamsBounded : CompParams {
 //    world unit apart in depth is 0.02 in the exponent: single pixels 1.2 and 2.2 tolerances off in two of six frames.
 // In fp64 both vanish (the position agrees with the oracle's to 1e-12 of a weight step). The price is about 45 fp64 fmas
 // and two divisions per lit pixel (DESIGN.md §5.8 has the timings); the G-buffer, the AO tap and the lights stay fp32.
-struct Mat4d { double m[16]; };
-struct CompParamsCascaded : CompParams {
-    Mat4d inv_proj_d, inv_view_d;          // the globals' fp32 entries, widened
-    Mat4d pv[SOC_MAX_SUN_CASCADES];
-    double rw_d, rh_d;                     // 1 / target width, 1 / target height
-    float split[SOC_MAX_SUN_CASCADES - 1];
-    float ef[SOC_MAX_SUN_CASCADES];
-    int count, S;
-};
 struct d3 { double x, y, z; };
 // the cascade of a stored depth: the number of splits below it (a NaN depth compares false: cascade 0)
 __device__ __forceinline__ int cascade_of(const CompParamsCascaded& p, float d) {
@@ -481,14 +451,6 @@ __device__ __forceinline__ float cascade_shadow(const CompParamsCascaded& p, int
     if (p.df != 1.0f) e = fast_pow(e, p.df);   // pow(x, 1.0) == x exactly
     return clampf(e, 0.0f, 1.0f);
 }
-// shade_pre without the shadow: direct = dot(n, -sun), to be multiplied by cascade_shadow
-__device__ __forceinline__ ShadePre shade_pre_unshadowed(const CompParams& p, f3 emissive, f3 n, float ssao) {
-    ShadePre s;
-    s.em = emissive * p.emissive_strength;
-    s.occl = fast_pow(ssao, p.ao_strength);
-    s.direct = fmaxf(0.0f, dot3(n, -mk3(p.sun_dir[0], p.sun_dir[1], p.sun_dir[2])));
-    return s;
-}
 // The sun shadows of up to NPX pixels of a lane, each with its own cascade ck[i] (live[i]: the pixel is lit) and world
 // position. The wave walks the cascades: one that no live pixel of the wave selects is skipped (wave-uniform branch),
 // the others run cascade_shadow under the mask of the lanes that selected them. A wave whose pixels share one cascade
@@ -510,6 +472,20 @@ __device__ __forceinline__ void cascade_shadows(const CompParamsCascaded& p, con
         for (int i = 0; i < NPX; ++i)
             if (mine[i]) out[i] = cascade_shadow(p, c, w[i], shadow);
     }
+}
+// The fused histogram's tail, by every lane of the workgroup: the bins of the lane's two stored pixels (mask: the pixels this
+// kernel wrote; lum_bin_fast with the exact fallback) into the wave's LDS histogram `sh + wave * kBins`, then the
+// workgroup's four histograms into one of the 8 scratch copies (linear block id mod 8), one device atomic per non-zero bin.
+__device__ __forceinline__ void bin_pair_and_flush(uint32_t* sh, int wave, const uint2* outp, uint32_t mask, const CompParams& p) {
+    const f4 c0 = unpack_h4(outp[0]), c1 = unpack_h4(outp[1]);
+    uint32_t b0 = lum_bin_fast(c0.x, c0.y, c0.z, p.bf);
+    uint32_t b1 = lum_bin_fast(c1.x, c1.y, c1.z, p.bf);
+    if (b0 == kBinExact) b0 = lum_bin(c0.x, c0.y, c0.z, p.lmin, p.lrange);
+    if (b1 == kBinExact) b1 = lum_bin(c1.x, c1.y, c1.z, p.lmin, p.lrange);
+    lane_bin_pair_mask(sh + wave * kBins, b0, b1, mask);
+    __syncthreads();
+    const uint32_t n = sh[threadIdx.x] + sh[kBins + threadIdx.x] + sh[2 * kBins + threadIdx.x] + sh[3 * kBins + threadIdx.x];
+    if (n) atomicAdd(&p.bins[((blockIdx.y * gridDim.x + blockIdx.x) & 7u) * kBins + threadIdx.x], n);
 }
 template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false, int LB = 0, bool CS = false>
 __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGHTS && !BL ? SOC_COMP_LIGHT_WAVES : 1))) void composition_pair(DImg target, DImg albedo, DImg emissive, DImg normal, DImg depth,
@@ -692,17 +668,7 @@ __global__ __launch_bounds__(kWorkgroup) __attribute__((amdgpu_waves_per_eu(LIGH
             if (own & 2u) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2w, outp[1]), bt.r, to + 8, 0, 0);
         }
     }
-    if (HIST) {
-        const f4 c0 = unpack_h4(outp[0]), c1 = unpack_h4(outp[1]);
-        uint32_t b0 = lum_bin_fast(c0.x, c0.y, c0.z, p.bf);
-        uint32_t b1 = lum_bin_fast(c1.x, c1.y, c1.z, p.bf);
-        if (b0 == kBinExact) b0 = lum_bin(c0.x, c0.y, c0.z, p.lmin, p.lrange);
-        if (b1 == kBinExact) b1 = lum_bin(c1.x, c1.y, c1.z, p.lmin, p.lrange);
-        lane_bin_pair_mask(sh + wave * kBins, b0, b1, inside ? own : 0u);
-        __syncthreads();
-        const uint32_t n = sh[threadIdx.x] + sh[kBins + threadIdx.x] + sh[2 * kBins + threadIdx.x] + sh[3 * kBins + threadIdx.x];
-        if (n) atomicAdd(&p.bins[((blockIdx.y * gridDim.x + blockIdx.x) & 7u) * kBins + threadIdx.x], n);
-    }
+    if (HIST) bin_pair_and_flush(sh, wave, outp, inside ? own : 0u, p);
 }
 // The sky pixels of the colour image (composition.inl:220-222: depth == 1 -> color = clouds texel), written and
 // binned on the renderer's second lane right after CloudRendering, so Composition (sky_external) does not wait
@@ -745,15 +711,7 @@ __global__ __launch_bounds__(kWorkgroup) void sky_compose_pair(DImg target, DImg
             }
         }
     }
-    const f4 c0 = unpack_h4(outp[0]), c1 = unpack_h4(outp[1]);
-    uint32_t b0 = lum_bin_fast(c0.x, c0.y, c0.z, p.bf);
-    uint32_t b1 = lum_bin_fast(c1.x, c1.y, c1.z, p.bf);
-    if (b0 == kBinExact) b0 = lum_bin(c0.x, c0.y, c0.z, p.lmin, p.lrange);
-    if (b1 == kBinExact) b1 = lum_bin(c1.x, c1.y, c1.z, p.lmin, p.lrange);
-    lane_bin_pair_mask(sh + wave * kBins, b0, b1, mine);
-    __syncthreads();
-    const uint32_t n = sh[threadIdx.x] + sh[kBins + threadIdx.x] + sh[2 * kBins + threadIdx.x] + sh[3 * kBins + threadIdx.x];
-    if (n) atomicAdd(&p.bins[((blockIdx.y * gridDim.x + blockIdx.x) & 7u) * kBins + threadIdx.x], n);
+    bin_pair_and_flush(sh, wave, outp, mine, p);
 }
 
 __global__ __launch_bounds__(kBins) void histogram_fold(uint32_t* __restrict__ scratch, uint32_t* __restrict__ bins) {
@@ -772,7 +730,7 @@ template <int LB>
 __device__ __forceinline__ void composition_generic_body(const DImg& target, const DImg& albedo, const DImg& emissive, const DImg& normal,
                                                          const DImg& depth, const DImg& ssao, const DImg& shadow, const DImg& clouds,
                                                          const CompParams& p, const LightBoundsDev* lb) {
-    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+    const int x = blockIdx.x * kGenericBlockX + threadIdx.x, y = blockIdx.y * kGenericBlockY + threadIdx.y;
     if (x >= target.w || y >= target.h) return;
     const float u = centre_uv(x, target.w), v = centre_uv(y, target.h);
     const float d = sample_f32(depth, u, v);
@@ -801,7 +759,7 @@ __global__ __launch_bounds__(kWorkgroup) void composition_generic_bounded(DImg t
 // cascaded sun shadows off the pair path: a pixel per lane, the wave's cascades walked as in composition_pair
 __global__ __launch_bounds__(kWorkgroup) void composition_generic_cascaded(DImg target, DImg albedo, DImg emissive, DImg normal,
                                                            DImg depth, DImg ssao, DImg shadow, DImg clouds, CompParamsCascaded p) {
-    const int x = blockIdx.x * BX + threadIdx.x, y = blockIdx.y * BY + threadIdx.y;
+    const int x = blockIdx.x * kGenericBlockX + threadIdx.x, y = blockIdx.y * kGenericBlockY + threadIdx.y;
     if (x >= target.w || y >= target.h) return;
     const float u = centre_uv(x, target.w), v = centre_uv(y, target.h);
     const float d = sample_f32(depth, u, v);
@@ -831,324 +789,105 @@ __global__ __launch_bounds__(kWorkgroup) void composition_generic_cascaded(DImg 
     row_ptr_w<uint2>(target, y)[x] = pack_h4(c);
 }
 
-bool aligned16(const soc_img& im) {
-    return (reinterpret_cast<uintptr_t>(im.data) & 15u) == 0 && (im.pitch_bytes & 15) == 0;
-}
-
 }  // namespace
 }  // namespace soc
 
 using namespace soc;
 
 namespace {
-using PairBounded = void (*)(DImg, DImg, DImg, DImg, DImg, DImg, DImg, DImg, CompParamsBounded, DImg, DImg);
-// the bounded form of the lights kernel a launch takes: lb = kLbBounded, with kLbCull and (stand-alone calls) kLbCount
-template <bool HIST, bool BL, bool SP>
-PairBounded pair_bounded(int lb) {
-    if constexpr (!BL && !SP) {
-        if (lb == (kLbBounded | kLbCount)) return composition_pair<HIST, true, 0, BL, SP, kLbBounded | kLbCount>;
-        if (lb == (kLbBounded | kLbCull | kLbCount)) return composition_pair<HIST, true, 0, BL, SP, kLbBounded | kLbCull | kLbCount>;
-    }
-    if (lb == (kLbBounded | kLbCull)) return composition_pair<HIST, true, 0, BL, SP, kLbBounded | kLbCull>;
-    return lb == kLbBounded ? composition_pair<HIST, true, 0, BL, SP, kLbBounded> : nullptr;
+// The pair kernel of a form, per parameter-block type: each instantiation is named here once, with the form it is
+// looked up by taken from the same template arguments. The plain forms: every pair of (hist, lights), the knobs' nt = 3
+// and 7 without lights, and under the histogram the in-kernel bloom and the zero cells; the cascaded forms: (hist,
+// lights); the bounded forms: the four lb of the stand-alone calls with and without the histogram, and bounded / cull
+// under the histogram's bl and sp.
+template <class P> using PairKernel = void (*)(DImg, DImg, DImg, DImg, DImg, DImg, DImg, DImg, P, DImg, DImg);
+template <class P> struct PairEntry {
+    PairForm form;
+    PairKernel<P> kernel;
+};
+template <bool HIST, bool LIGHTS, int NT = 0, bool BL = false, bool SP = false, int LB = 0, bool CS = false>
+PairEntry<std::conditional_t<CS, CompParamsCascaded, std::conditional_t<LB != 0, CompParamsBounded, CompParams>>> pair_entry() {
+    return {PairForm{HIST, LIGHTS, NT, BL, SP, LB, CS}, composition_pair<HIST, LIGHTS, NT, BL, SP, LB, CS>};
 }
-// what a bounded call adds to composition_launch's arguments (null: the unbounded kernels)
-using BoundedCall = soc::LightBoundsCall;
+constexpr int kCull = kLbBounded | kLbCull, kCount = kLbBounded | kLbCount, kCullCount = kLbBounded | kLbCull | kLbCount;
+const PairEntry<CompParams> kPlainPairs[] = {
+    pair_entry<false, false>(), pair_entry<false, true>(), pair_entry<true, false>(), pair_entry<true, true>(),
+    pair_entry<false, false, 3>(), pair_entry<false, false, 7>(), pair_entry<true, false, 3>(), pair_entry<true, false, 7>(),
+    pair_entry<true, false, 7, true>(), pair_entry<true, false, 7, true, true>(),
+    pair_entry<true, true, 0, true>(), pair_entry<true, true, 0, true, true>(), pair_entry<true, true, 0, false, true>()};
+const PairEntry<CompParamsCascaded> kCascadedPairs[] = {
+    pair_entry<false, false, 7, false, false, 0, true>(), pair_entry<false, true, 0, false, false, 0, true>(),
+    pair_entry<true, false, 7, false, false, 0, true>(), pair_entry<true, true, 0, false, false, 0, true>()};
+const PairEntry<CompParamsBounded> kBoundedPairs[] = {
+    pair_entry<false, true, 0, false, false, kLbBounded>(), pair_entry<false, true, 0, false, false, kCull>(),
+    pair_entry<false, true, 0, false, false, kCount>(), pair_entry<false, true, 0, false, false, kCullCount>(),
+    pair_entry<true, true, 0, false, false, kLbBounded>(), pair_entry<true, true, 0, false, false, kCull>(),
+    pair_entry<true, true, 0, false, false, kCount>(), pair_entry<true, true, 0, false, false, kCullCount>(),
+    pair_entry<true, true, 0, true, false, kLbBounded>(), pair_entry<true, true, 0, true, false, kCull>(),
+    pair_entry<true, true, 0, false, true, kLbBounded>(), pair_entry<true, true, 0, false, true, kCull>(),
+    pair_entry<true, true, 0, true, true, kLbBounded>(), pair_entry<true, true, 0, true, true, kCull>()};
 
-// The cascaded instantiations' parameter block: the record's matrices (and the camera's inverses) widened to fp64, the
-// factors as they are (the unused entries repeat the last cascade) and +inf for the splits that do not exist.
-CompParamsCascaded cascaded_params(const CompParams& p, const soc_sun_cascades& cs, int W, int H) {
-    CompParamsCascaded pc;
-    static_cast<CompParams&>(pc) = p;
-    pc.count = cs.count;
-    pc.S = cs.map_size;
-    for (int i = 0; i < 16; ++i) {
-        pc.inv_proj_d.m[i] = (double)p.inv_proj.m[i];
-        pc.inv_view_d.m[i] = (double)p.inv_view.m[i];
+template <class P, size_t N>
+PairKernel<P> pair_kernel(const PairEntry<P> (&table)[N], const PairForm& f) {
+    for (const PairEntry<P>& e : table) {
+        const PairForm& t = e.form;
+        if (t.hist == f.hist && t.lights == f.lights && t.nt == f.nt && t.bl == f.bl && t.sp == f.sp && t.lb == f.lb && t.cs == f.cs)
+            return e.kernel;
     }
-    pc.rw_d = 1.0 / (double)W;
-    pc.rh_d = 1.0 / (double)H;
-    for (int k = 0; k < SOC_MAX_SUN_CASCADES; ++k) {
-        const int c = k < cs.count ? k : cs.count - 1;
-        for (int i = 0; i < 16; ++i) pc.pv[k].m[i] = (double)cs.projection_view[c][i];
-        pc.ef[k] = cs.exponential_factor[c];
-        if (k < SOC_MAX_SUN_CASCADES - 1) pc.split[k] = k < cs.count - 1 ? cs.split_depth[k] : __builtin_inff();
-    }
-    return pc;
+    return nullptr;   // a form no kernel exists for
 }
 
-// bins != nullptr: the fused histogram variant if the pair path applies at the globals' resolution
-// (returns 1 otherwise, having launched nothing)
-// bloom_mip1 != nullptr (the render graph under SOC_RENDERER_BLOOM_IN_COMPOSITION): the bloom output is computed in the
-// kernel from the chain's mip1 (composition_pair<..., BL>); needs the fused histogram and the pair path.
-// bloom_mip3 != nullptr (the render graph under SOC_BLOOM_SPARSE): cells proven zero from the chain's mip3 take the
-// constant in place of the `emissive` load (the sparse last stage did not write them) or of the in-kernel upsample.
-int composition_launch(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo, soc_img emissive,
-                       soc_img normal, soc_img depth, soc_img ssao, soc_img shadow, soc_img clouds, uint32_t* bins,
-                       uint32_t* scratch, soc_stream stream, bool fold = true, bool sky_external = false,
-                       const soc_img* bloom_mip1 = nullptr, const soc_img* bloom_mip3 = nullptr,
-                       const BoundedCall* bc = nullptr, const soc_sun_cascades* cs = nullptr, bool cascaded = false) {
-    static const char* P = "soc_composition";
-    if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
-    int rc = SOC_OK;
-    if (cascaded) {   // the record and its atlas first, so that the message names the cascades' field
-        rc = check_sun_cascades(cs, &shadow, P);
-        if (rc) return rc;
-        if (bc) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with bounded lights are not supported", P);
-        if (bloom_mip1) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with the in-kernel bloom are not supported", P);
-        if (bloom_mip3) return set_error(SOC_E_UNSUPPORTED, "%s: sun cascades with the bloom's zero cells are not supported", P);
-    }
-    rc = check_img(target, SOC_FMT_RGBA16F, P, "target");
-    if (!rc) rc = check_img(albedo, SOC_FMT_RGBA16F, P, "albedo");
-    if (!rc) rc = check_img(emissive, SOC_FMT_RGBA16F, P, "emissive");
-    if (!rc) rc = check_img(normal, SOC_FMT_RGBA16F, P, "normal");
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, P, "depth");
-    if (!rc) rc = check_img(ssao, SOC_FMT_R8_UNORM, P, "ssao");
-    if (!rc) rc = check_img(shadow, SOC_FMT_D32F, P, "shadow");
-    if (!rc) rc = check_img(clouds, SOC_FMT_RGBA8_UNORM, P, "clouds");
-    if (rc) return rc;
-    CompParams p;
-    p.inv_proj = mat4(g->camera_inverse_projection_matrix);
-    p.inv_view = mat4(g->camera_inverse_view_matrix);
-    mat4_mul_host(p.sun_pv.m, g->sun_info.projection_matrix, g->sun_info.view_matrix);
-    {
-        float t[16];
-        mat4_mul_host(t, p.sun_pv.m, g->camera_inverse_view_matrix);
-        mat4_mul_host(p.sun_clip.m, t, g->camera_inverse_projection_matrix);
-    }
-    for (int i = 0; i < 3; ++i) {
-        p.sun_dir[i] = g->sun_info.direction[i];
-        p.ambient[i] = g->ambient[i];
-        p.cam[i] = g->camera_position[i];
-    }
-    p.ef = g->sun_info.exponential_factor;
-    p.df = g->sun_info.darkening_factor;
-    p.emissive_strength = g->emissive_bloom_strength;
-    p.ao_strength = g->ambient_occlussion_strength;
-    p.npl = g->point_light_count < SOC_MAX_POINT_LIGHTS ? g->point_light_count : SOC_MAX_POINT_LIGHTS;
-    p.nsl = g->spot_light_count < SOC_MAX_SPOT_LIGHTS ? g->spot_light_count : SOC_MAX_SPOT_LIGHTS;
-    p.dg = d_globals;
-    // non-temporal G-buffer loads and colour store (default); SOC_COMP_NT=0 selects the default cache policy for the
-    // variant-identity test
-    const bool nt = tuning_knob("SOC_COMP_NT", 3) == 3;
-    // SOC_COMP_AOP=0: the AO taps as 4 byte loads per pixel after the depth test (round 4); 1: sample_r8_pair
-    const bool aop = tuning_knob("SOC_COMP_AOP", 1) != 0;
-    p.swz = 0;   // row-major (the strip order measured 66 -> 77 us)
-    p.rw = recip_rn(target.width);
-    p.rh = recip_rn(target.height);
-    p.bloom_zero_skip = tuning_knob("SOC_BLOOM_ZERO_SKIP", 1) != 0;
-    p.bins = nullptr;
-    p.sky_external = 0;
-    if ((p.npl || p.nsl) && !d_globals)
-        return set_error(SOC_E_INVALID_ARG, "%s: frame has lights but no device globals (soc_upload_globals)", P);
-    if (bc && !bc->d_bounds) return set_error(SOC_E_INVALID_ARG, "%s: bounded call without light bounds (soc_upload_light_bounds)", P);
-    if (bc && (bc->flags & ~(uint32_t)SOC_LIGHTS_CULL)) return set_error(SOC_E_INVALID_ARG, "%s: unknown light flags %u", P, bc->flags);
-
-    const int W = target.width, H = target.height;
-    auto same = [&](const soc_img& im) { return im.width == W && im.height == H; };
-    const bool fast = same(albedo) && same(emissive) && same(normal) && same(depth) && same(clouds) && (W % 2 == 0) &&
-                      W <= 8192 && H <= 8192 && aligned16(target) && aligned16(albedo) && aligned16(emissive) &&
-                      aligned16(normal) && (reinterpret_cast<uintptr_t>(depth.data) & 7u) == 0 && (depth.pitch_bytes & 7) == 0;
-    if (bins && !(fast && W == g->resolution[0] && H == g->resolution[1])) return 1;
-    if (sky_external && !bins) return set_error(SOC_E_INVALID_ARG, "%s: sky_external needs the fused histogram", P);
-    if (bloom_mip1) {
-        rc = check_img(*bloom_mip1, SOC_FMT_RGBA16F, P, "bloom mip1");
-        if (rc) return rc;
-        if (!bins || !fast || bloom_mip1->width * 2 != W || bloom_mip1->height * 2 != H)
-            return set_error(SOC_E_SHAPE, "%s: the in-kernel bloom needs the fused histogram's pair path and mip1 = W/2 x H/2", P);
-    }
-    if (bloom_mip3) {
-        rc = check_img(*bloom_mip3, SOC_FMT_RGBA16F, P, "bloom mip3");
-        if (rc) return rc;
-        if (!bins || !fast || bloom_mip3->width * 8 != W || bloom_mip3->height * 8 != H)
-            return set_error(SOC_E_SHAPE, "%s: the bloom's zero cells need the fused histogram's pair path and mip3 = W/8 x H/8", P);
-    }
-    p.bloom_sparse = bloom_mip3 != nullptr;
-    const DImg m3 = bloom_mip3 ? dimg(*bloom_mip3) : DImg{};
-    if (fast) {
-        dim3 grd(ceil_div(W, 32), ceil_div(H, 16));
-        const bool lights = (p.npl | p.nsl) != 0;
-        // bounded lights: a frame without lights has nothing to bound and takes the kernels below
-        PairBounded kb = nullptr;
-        if (bc && lights) {
-            const int lb = kLbBounded | ((bc->flags & SOC_LIGHTS_CULL) ? kLbCull : 0) | (bc->d_shaded_pairs ? kLbCount : 0);
-            if (!bins) kb = pair_bounded<false, false, false>(lb);
-            else if (bloom_mip1 && bloom_mip3) kb = pair_bounded<true, true, true>(lb);
-            else if (bloom_mip1) kb = pair_bounded<true, true, false>(lb);
-            else if (bloom_mip3) kb = pair_bounded<true, false, true>(lb);
-            else kb = pair_bounded<true, false, false>(lb);
-            if (!kb) return set_error(SOC_E_INVALID_ARG, "%s: the shaded-pairs counter is the stand-alone calls'", P);
-        }
-        if (cascaded) {   // the pair path's cascaded forms: with and without the histogram, with and without lights
-            if (bins) {
-                p.bins = scratch;
-                p.sky_external = sky_external ? 1 : 0;
-                p.lmin = g->log_min_luminance;
-                p.lrange = g->log_max_luminance - g->log_min_luminance;
-                p.bf = bin_fast_params(p.lmin, p.lrange);
-            }
-            const CompParamsCascaded pc = cascaded_params(p, *cs, W, H);
-#define SOC_COMP_PAIR_CS(HI, LI, N) launch("composition_pair", kWorkgroup, composition_pair<HI, LI, N, false, false, 0, true>, grd, kWorkgroup, 0, \
-            hs(stream), dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), pc, DImg{}, DImg{})
-            if (bins && lights) SOC_COMP_PAIR_CS(true, true, 0);
-            else if (bins) SOC_COMP_PAIR_CS(true, false, 7);
-            else if (lights) SOC_COMP_PAIR_CS(false, true, 0);
-            else SOC_COMP_PAIR_CS(false, false, 7);
-#undef SOC_COMP_PAIR_CS
-            if (bins && fold) launch("histogram_fold", kBins, histogram_fold, 1, kBins, 0, hs(stream), scratch, bins);
-            return check_launch("composition");
-        }
-        auto launch_bounded = [&](const DImg& m1) {
-            CompParamsBounded pb;
-            static_cast<CompParams&>(pb) = p;
-            pb.la = LightArgs{static_cast<const LightBoundsDev*>(bc->d_bounds), bc->d_shaded_pairs};
-            launch("composition_pair", kWorkgroup, kb, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                   dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), pb, m1, m3);
-        };
-#define SOC_COMP_PAIR(HI, LI) launch("composition_pair", kWorkgroup, composition_pair<HI, LI>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), \
-            dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3)
-        if (bins) {
-            p.bins = scratch;
-            p.sky_external = sky_external ? 1 : 0;
-            p.lmin = g->log_min_luminance;
-            p.lrange = g->log_max_luminance - g->log_min_luminance;
-            p.bf = bin_fast_params(p.lmin, p.lrange);
-            if (kb)
-                launch_bounded(bloom_mip1 ? dimg(*bloom_mip1) : DImg{});
-            else if (bloom_mip1 && lights && bloom_mip3)
-                launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, true, true>, grd, kWorkgroup, 0, hs(stream),
-                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, dimg(*bloom_mip1), m3);
-            else if (bloom_mip1 && lights)
-                launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, true>, grd, kWorkgroup, 0, hs(stream),
-                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, dimg(*bloom_mip1), m3);
-            else if (bloom_mip1 && bloom_mip3)
-                launch("composition_pair", kWorkgroup, composition_pair<true, false, 7, true, true>, grd, kWorkgroup, 0, hs(stream),
-                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, dimg(*bloom_mip1), m3);
-            else if (bloom_mip1)
-                launch("composition_pair", kWorkgroup, composition_pair<true, false, 7, true>, grd, kWorkgroup, 0, hs(stream),
-                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, dimg(*bloom_mip1), m3);
-            else if (lights && bloom_mip3)
-                launch("composition_pair", kWorkgroup, composition_pair<true, true, 0, false, true>, grd, kWorkgroup, 0, hs(stream),
-                       dimg(target), dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow),
-                       dimg(clouds), p, DImg{}, m3);
-            else if (lights) SOC_COMP_PAIR(true, true);
-            else if (nt && aop)
-                launch("composition_pair", kWorkgroup, composition_pair<true, false, 7>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                    dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
-            else if (nt)
-                launch("composition_pair", kWorkgroup, composition_pair<true, false, 3>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                    dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
-            else SOC_COMP_PAIR(true, false);
-            if (fold) launch("histogram_fold", kBins, histogram_fold, 1, kBins, 0, hs(stream), scratch, bins);
-        } else if (kb) {
-            launch_bounded(DImg{});
-        } else if (nt && !lights && aop) {
-            launch("composition_pair", kWorkgroup, composition_pair<false, false, 7>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
-        } else if (nt && !lights) {
-            // non-temporal G-buffer loads and colour store (measured at 4K: 71.5 -> 68 us; TAA, the next
-            // reader of depth, +3 us: the frame is unchanged). SOC_COMP_NT=0: default cache policy.
-            launch("composition_pair", kWorkgroup, composition_pair<false, false, 3>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive),
-                dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p, DImg{}, m3);
-        } else {
-            if (lights) SOC_COMP_PAIR(false, true);
-            else SOC_COMP_PAIR(false, false);
-        }
-#undef SOC_COMP_PAIR
+// Launches what plan_composition decided: the kernel, then the fold of the 8 partial histograms.
+int issue_composition(const CompositionPlan& pl, soc_stream stream) {
+    const dim3 grd(pl.grid_x, pl.grid_y), blk(pl.block_x, pl.block_y);
+    auto go = [&](const char* name, auto kernel, const auto&... tail) {
+        if (!kernel) return set_error(SOC_E_INVALID_ARG, "soc_composition: no %s of the planned form", name);
+        const DImg* im = pl.img;
+        launch(name, kWorkgroup, kernel, grd, blk, 0, hs(stream), im[0], im[1], im[2], im[3], im[4], im[5], im[6], im[7], tail...);
+        return (int)SOC_OK;
+    };
+    const CompParams& p = pl.p;
+    int rc;
+    if (pl.kernel == kCompGeneric) {
+        rc = go("composition_generic", composition_generic, p);
+    } else if (pl.kernel == kCompGenericBounded) {
+        rc = go("composition_generic_bounded", composition_generic_bounded, p, pl.la.lb);
+    } else if (pl.kernel == kCompGenericCascaded) {
+        rc = go("composition_generic_cascaded", composition_generic_cascaded, pl.p);
+    } else if (pl.form.cs) {
+        rc = go("composition_pair", pair_kernel(kCascadedPairs, pl.form), pl.p, pl.mip1, pl.mip3);
+    } else if (pl.form.lb) {
+        CompParamsBounded pb;
+        static_cast<CompParams&>(pb) = p;
+        pb.la = pl.la;
+        rc = go("composition_pair", pair_kernel(kBoundedPairs, pl.form), pb, pl.mip1, pl.mip3);
     } else {
-        dim3 blk(BX, BY), grd(ceil_div(W, BX), ceil_div(H, BY));
-        if (cascaded)
-            launch("composition_generic_cascaded", kWorkgroup, composition_generic_cascaded, grd, blk, 0, hs(stream), dimg(target),
-                   dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds),
-                   cascaded_params(p, *cs, W, H));
-        else if (bc && (p.npl | p.nsl))
-            launch("composition_generic_bounded", kWorkgroup, composition_generic_bounded, grd, blk, 0, hs(stream), dimg(target),
-                   dimg(albedo), dimg(emissive), dimg(normal), dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p,
-                   static_cast<const LightBoundsDev*>(bc->d_bounds));
-        else launch("composition_generic", kWorkgroup, composition_generic, grd, blk, 0, hs(stream), dimg(target), dimg(albedo), dimg(emissive), dimg(normal),
-                                                         dimg(depth), dimg(ssao), dimg(shadow), dimg(clouds), p);
+        rc = go("composition_pair", pair_kernel(kPlainPairs, pl.form), p, pl.mip1, pl.mip3);
     }
+    if (rc) return rc;
+    if (pl.fold) launch("histogram_fold", kBins, histogram_fold, 1, kBins, 0, hs(stream), pl.scratch, pl.bins);
     return check_launch("composition");
 }
+
 }  // namespace
 
-bool soc::composition_pair_applicable(const soc_globals* g, const soc_img& target, const soc_img& albedo,
-                                      const soc_img& emissive, const soc_img& normal, const soc_img& depth,
-                                      const soc_img& clouds) {
-    const int W = target.width, H = target.height;
-    auto same = [&](const soc_img& im) { return im.width == W && im.height == H; };
-    return g && same(albedo) && same(emissive) && same(normal) && same(depth) && same(clouds) && (W % 2 == 0) &&
-           W <= 8192 && H <= 8192 && aligned16(target) && aligned16(albedo) && aligned16(emissive) &&
-           aligned16(normal) && (reinterpret_cast<uintptr_t>(depth.data) & 7u) == 0 && (depth.pitch_bytes & 7) == 0 &&
-           W == g->resolution[0] && H == g->resolution[1];
+int soc::composition(const CompositionCall& c, soc_stream stream) {
+    CompositionPlan pl;
+    int rc = plan_composition(c, pl);
+    if (!rc) rc = issue_composition(pl, stream);
+    // not fusable: the two passes back to back (same results)
+    if (!rc && pl.histogram_pass) rc = soc_generate_luminance_histogram(c.g, c.target, c.ae, stream);
+    return rc;
 }
 
 int soc::sky_compose_launch(const soc_globals* g, soc_img target, soc_img depth, soc_img clouds, uint32_t* scratch,
                             soc_stream stream) {
-    if (!g || !scratch) return set_error(SOC_E_INVALID_ARG, "sky compose: null globals / scratch");
-    int rc = check_img(target, SOC_FMT_RGBA16F, "sky compose", "target");
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, "sky compose", "depth");
-    if (!rc) rc = check_img(clouds, SOC_FMT_RGBA8_UNORM, "sky compose", "clouds");
+    SkyComposePlan pl;
+    const int rc = plan_sky_compose(g, target, depth, clouds, scratch, pl);
     if (rc) return rc;
-    CompParams p{};
-    p.bins = scratch;
-    p.lmin = g->log_min_luminance;
-    p.lrange = g->log_max_luminance - g->log_min_luminance;
-    p.bf = bin_fast_params(p.lmin, p.lrange);
-    const dim3 grd(ceil_div(target.width, 32), ceil_div(target.height, 16));
-    const bool cp = (clouds.pitch_bytes % 8) == 0 && (reinterpret_cast<uintptr_t>(clouds.data) % 8) == 0 &&
-                    tuning_knob("SOC_SKY_COMPOSE_PAIR_LOAD", 1);
-    if (cp)
-        launch("sky_compose_pair", kWorkgroup, sky_compose_pair<true>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(depth),
-               dimg(clouds), p);
-    else
-        launch("sky_compose_pair", kWorkgroup, sky_compose_pair<false>, grd, kWorkgroup, 0, hs(stream), dimg(target), dimg(depth),
-               dimg(clouds), p);
+    launch("sky_compose_pair", kWorkgroup, pl.pair_load ? sky_compose_pair<true> : sky_compose_pair<false>,
+           dim3(pl.grid_x, pl.grid_y), kWorkgroup, 0, hs(stream), pl.target, pl.depth, pl.clouds, pl.p);
     return check_launch("sky_compose");
-}
-
-extern "C" int soc_composition(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
-                               soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
-                               soc_img clouds, soc_stream stream) {
-    return composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
-                              stream);
-}
-
-extern "C" int soc_composition_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
-                                       soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
-                                       soc_img clouds, const void* d_bounds, uint32_t flags, uint32_t* d_shaded_pairs,
-                                       soc_stream stream) {
-    const BoundedCall bc = {d_bounds, flags, d_shaded_pairs};
-    return composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
-                              stream, true, false, nullptr, nullptr, &bc);
-}
-
-int soc::composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target,
-                                         soc_img albedo, soc_img emissive, soc_img normal, soc_img depth, soc_img ssao,
-                                         soc_img shadow, soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch,
-                                         bool fold, soc_stream stream, bool sky_external, const soc_img* bloom_mip1,
-                                         const soc_img* bloom_mip3, const LightBoundsCall* bounds,
-                                         const soc_sun_cascades* cascades) {
-    if (!g || !ae || !scratch)
-        return set_error(SOC_E_INVALID_ARG, "soc_composition_luminance_histogram: null globals / auto exposure / scratch");
-    const BoundedCall* bc = bounds;
-    const bool cs = cascades != nullptr;
-    int rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds,
-                                ae->histogram_buckets, scratch, stream, fold, sky_external, bloom_mip1, bloom_mip3, bc,
-                                cascades, cs);
-    if (rc <= 0) return rc;   // launched (or failed validation)
-    if (bloom_mip3) return set_error(SOC_E_SHAPE, "composition: the bloom's zero cells need the pair path");
-    if (bloom_mip1) return set_error(SOC_E_SHAPE, "composition: the in-kernel bloom needs the pair path");
-    if (sky_external) return set_error(SOC_E_INVALID_ARG, "composition: sky_external needs the pair path");
-    // not fusable: the two passes back to back (same results)
-    rc = composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
-                            stream, true, false, nullptr, nullptr, bc, cascades, cs);
-    if (rc) return rc;
-    return soc_generate_luminance_histogram(g, target, ae, stream);
 }
 
 int soc::histogram_fold_launch(uint32_t* scratch, soc_auto_exposure* ae, soc_stream stream) {
@@ -1157,12 +896,40 @@ int soc::histogram_fold_launch(uint32_t* scratch, soc_auto_exposure* ae, soc_str
     return check_launch("luminance_histogram_fold");
 }
 
+extern "C" int soc_composition(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                               soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                               soc_img clouds, soc_stream stream) {
+    return composition(composition_call(g, d_globals, {target, albedo, emissive, normal, depth, ssao, shadow, clouds}), stream);
+}
+
+extern "C" int soc_composition_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                                       soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                                       soc_img clouds, const void* d_bounds, uint32_t flags, uint32_t* d_shaded_pairs,
+                                       soc_stream stream) {
+    const LightBoundsCall bc = {d_bounds, flags, d_shaded_pairs};
+    CompositionCall c = composition_call(g, d_globals, {target, albedo, emissive, normal, depth, ssao, shadow, clouds});
+    c.bounds = &bc;
+    return composition(c, stream);
+}
+
+extern "C" int soc_composition_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
+                                        soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
+                                        soc_img clouds, const soc_sun_cascades* cascades, soc_stream stream) {
+    CompositionCall c = composition_call(g, d_globals, {target, albedo, emissive, normal, depth, ssao, shadow, clouds});
+    c.cascades = cascades;
+    c.cascaded = true;
+    return composition(c, stream);
+}
+
 extern "C" int soc_composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target,
                                                    soc_img albedo, soc_img emissive, soc_img normal, soc_img depth,
                                                    soc_img ssao, soc_img shadow, soc_img clouds, soc_auto_exposure* ae,
                                                    uint32_t* scratch, soc_stream stream) {
-    return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
-                                           scratch, true, stream);
+    CompositionCall c = composition_call(g, d_globals, {target, albedo, emissive, normal, depth, ssao, shadow, clouds});
+    c.histogram = c.fold = true;
+    c.ae = ae;
+    c.scratch = scratch;
+    return composition(c, stream);
 }
 
 extern "C" int soc_composition_luminance_histogram_bounded(const soc_globals* g, const soc_globals* d_globals, soc_img target,
@@ -1171,15 +938,12 @@ extern "C" int soc_composition_luminance_histogram_bounded(const soc_globals* g,
                                                            uint32_t* scratch, const void* d_bounds, uint32_t flags,
                                                            uint32_t* d_shaded_pairs, soc_stream stream) {
     const LightBoundsCall bc = {d_bounds, flags, d_shaded_pairs};
-    return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
-                                           scratch, true, stream, false, nullptr, nullptr, &bc);
-}
-
-extern "C" int soc_composition_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
-                                        soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
-                                        soc_img clouds, const soc_sun_cascades* cascades, soc_stream stream) {
-    return composition_launch(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, nullptr, nullptr,
-                              stream, true, false, nullptr, nullptr, nullptr, cascades, true);
+    CompositionCall c = composition_call(g, d_globals, {target, albedo, emissive, normal, depth, ssao, shadow, clouds});
+    c.histogram = c.fold = true;
+    c.ae = ae;
+    c.scratch = scratch;
+    c.bounds = &bc;
+    return composition(c, stream);
 }
 
 extern "C" int soc_composition_luminance_histogram_cascaded(const soc_globals* g, const soc_globals* d_globals, soc_img target,
@@ -1188,6 +952,11 @@ extern "C" int soc_composition_luminance_histogram_cascaded(const soc_globals* g
                                                             uint32_t* scratch, const soc_sun_cascades* cascades,
                                                             soc_stream stream) {
     if (!cascades) return set_error(SOC_E_INVALID_ARG, "soc_composition_luminance_histogram_cascaded: null cascades");
-    return composition_luminance_histogram(g, d_globals, target, albedo, emissive, normal, depth, ssao, shadow, clouds, ae,
-                                           scratch, true, stream, false, nullptr, nullptr, nullptr, cascades);
+    CompositionCall c = composition_call(g, d_globals, {target, albedo, emissive, normal, depth, ssao, shadow, clouds});
+    c.histogram = c.fold = true;
+    c.ae = ae;
+    c.scratch = scratch;
+    c.cascades = cascades;
+    c.cascaded = true;
+    return composition(c, stream);
 }

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "composition_plan.hpp"
 #include "renderer.hpp"
 
 using namespace soc;
@@ -231,6 +232,13 @@ void build_passes(soc_renderer* r) {
              });
 }
 
+// the frame's Composition call: the globals and the images (the bloom output is the emissive input)
+soc::CompositionCall composition_call(const soc_renderer* r, const soc_globals* g) {
+    const auto& I = r->img;
+    return soc::composition_call(g, I.d_globals,
+                                 {I.color, I.albedo, r->bloom_image(), I.normal, I.depth, I.ssao_blur, I.shadow, I.clouds});
+}
+
 void build_passes_tail(soc_renderer* r) {
     auto& I = r->img;
     const int pre = SOC_PHASE_PRE_EXPOSURE, post = SOC_PHASE_POST_EXPOSURE;
@@ -281,16 +289,18 @@ void build_passes_tail(soc_renderer* r) {
     if (fused_hist) {
         add_pass(r, "Composition+GenerateLuminanceHistogram", "Composition", pre, comp_reads,
                  res_mask({SOC_RES_COLOR, SOC_RES_HISTOGRAM_PARTIALS}), [r](const soc_globals* g, hipStream_t s) {
-                     const auto& I = r->img;
                      const soc::LightBoundsCall lb = {r->light_bounds, r->light_flags, nullptr};
-                     return soc::composition_luminance_histogram(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
-                                                                 I.ssao_blur, I.shadow, I.clouds, I.auto_exposure,
-                                                                 r->hist_scratch, false, (soc_stream)s,
-                                                                 r->sky_split_active,
-                                                                 bloom_in_comp_active(r) ? &I.bloom_mips[1] : nullptr,
-                                                                 r->bloom_cells_frame ? &I.bloom_mips[3] : nullptr,
-                                                                 r->light_bounds ? &lb : nullptr,
-                                                                 r->has_cascades ? &r->cascades : nullptr);
+                     soc::CompositionCall c = composition_call(r, g);
+                     c.histogram = true;
+                     c.ae = r->img.auto_exposure;
+                     c.scratch = r->hist_scratch;
+                     c.sky_external = r->sky_split_active;
+                     c.bloom_mip1 = bloom_in_comp_active(r) ? &r->img.bloom_mips[1] : nullptr;
+                     c.bloom_mip3 = r->bloom_cells_frame ? &r->img.bloom_mips[3] : nullptr;
+                     c.bounds = r->light_bounds ? &lb : nullptr;
+                     c.cascades = r->has_cascades ? &r->cascades : nullptr;
+                     c.cascaded = r->has_cascades;
+                     return soc::composition(c, (soc_stream)s);
                  });
         // the 8 partial histograms of the fused launch into the AutoExposure bins. Before a multi-GPU exchange
         // (PRE and POST in separate calls) the fold must precede it; in a one-call frame the resolve folds them
@@ -305,16 +315,13 @@ void build_passes_tail(soc_renderer* r) {
     } else {
         add_pass(r, "Composition", "Composition", pre, comp_reads, res_mask({SOC_RES_COLOR}),
                  [r](const soc_globals* g, hipStream_t s) {
-                     const auto& I = r->img;
-                     if (r->has_cascades)
-                         return soc_composition_cascaded(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
-                                                         I.ssao_blur, I.shadow, I.clouds, &r->cascades, (soc_stream)s);
-                     if (r->light_bounds)
-                         return soc_composition_bounded(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth,
-                                                        I.ssao_blur, I.shadow, I.clouds, r->light_bounds, r->light_flags, nullptr,
-                                                        (soc_stream)s);
-                     return soc_composition(g, I.d_globals, I.color, I.albedo, r->bloom_image(), I.normal, I.depth, I.ssao_blur,
-                                            I.shadow, I.clouds, (soc_stream)s);
+                     // the cascades come without bounded lights (soc_composition_cascaded, else soc_composition_bounded)
+                     const soc::LightBoundsCall lb = {r->light_bounds, r->light_flags, nullptr};
+                     soc::CompositionCall c = composition_call(r, g);
+                     c.bounds = r->light_bounds && !r->has_cascades ? &lb : nullptr;
+                     c.cascades = r->has_cascades ? &r->cascades : nullptr;
+                     c.cascaded = r->has_cascades;
+                     return soc::composition(c, (soc_stream)s);
                  });
         add_pass(r, "GenerateLuminanceHistogram", "Auto Exposure", pre, res_mask({SOC_RES_COLOR}),
                  res_mask({SOC_RES_AUTO_EXPOSURE}), [r](const soc_globals* g, hipStream_t s) {

@@ -110,18 +110,11 @@ struct LightBoundsCall {
     uint32_t* d_shaded_pairs;
 };
 
-// soc_composition_luminance_histogram with the fold of the 8 partial histograms optionally left to a
-// separate histogram_fold_launch (the render graph times the fold as a pass of its own).
-int composition_luminance_histogram(const soc_globals* g, const soc_globals* d_globals, soc_img target, soc_img albedo,
-                                    soc_img emissive, soc_img normal, soc_img depth, soc_img ssao, soc_img shadow,
-                                    soc_img clouds, soc_auto_exposure* ae, uint32_t* scratch, bool fold, soc_stream stream,
-                                    bool sky_external = false, const soc_img* bloom_mip1 = nullptr,
-                                    const soc_img* bloom_mip3 = nullptr, const LightBoundsCall* bounds = nullptr,
-                                    const soc_sun_cascades* cascades = nullptr);
 // A soc_sun_cascades record (and, when given, its atlas) against soc_rt.h's rules, on the host: SOC_E_INVALID_ARG naming
 // the field, with `pass` in front (host_math.cpp).
 int check_sun_cascades(const soc_sun_cascades* c, const soc_img* atlas, const char* pass);
-// The fused pair path applies to these images at the globals' resolution (composition.hip).
+// The fused pair path applies to these images at the globals' resolution (composition_plan.cpp; the Composition call
+// itself is composition_plan.hpp's record).
 bool composition_pair_applicable(const soc_globals* g, const soc_img& target, const soc_img& albedo,
                                  const soc_img& emissive, const soc_img& normal, const soc_img& depth,
                                  const soc_img& clouds);

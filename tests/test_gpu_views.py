@@ -26,8 +26,8 @@ mixed, whose calls take the unaligned side as soon as one gated image is unalign
   soc_ssao_blur: ssao_blur_kernel, no gate (odd pitch and base in odd).
   soc_cloud_rendering (clouds.hip): clouds_classify's vec_store is target % 16 (pad16 1, odd 0); clouds_od_lut<R8 / RGBA8>
       reads the padded noise view; with and without the workspace (the pair lists / the single-lane kernel).
-  soc_composition (composition.hip composition_launch): pad16 composition_pair<.., 7> (lights: <false, true>); odd and
-      mixed composition_generic at even widths (aligned16 / depth & 7 fail; with lights: LIT_GENERIC_RELAXED). soc_composition_luminance_histogram: pad16
+  soc_composition (composition_plan.cpp plan_composition): pad16 composition_pair<.., 7> (lights: <false, true>); odd and
+      mixed composition_generic at even widths (composition_pair_path: aligned16 / depth & 7 fail; with lights: LIT_GENERIC_RELAXED). soc_composition_luminance_histogram: pad16
       the fused pair kernel + histogram_fold; odd / mixed the two-pass fallback (composition_generic, then the histogram).
   soc_generate_luminance_histogram (exposure.hip): 64x36 pad16 histogram_chunks, odd histogram_pixels at W % 8 == 0;
       97x55 histogram_pixels everywhere.

@@ -1,6 +1,6 @@
 // san_host — drives the host code under AddressSanitizer + UndefinedBehaviorSanitizer (tools/sanitize/Makefile).
 // No GPU call is made: the globals feed and ECS scene feed, ABI introspection, the render graph (construction,
-// caller passes, derived and ring dependencies, raster head, error paths), the clouds planner, the raster workspaces and
+// caller passes, derived and ring dependencies, raster head, error paths), the clouds and Composition planners, the raster workspaces and
 // the draw scenes' host checks, the PNG / EXR writers, the scene synthesiser, and every pass of the CPU oracle on small
 // images (odd extents included). Exit 0 when every check passes; a sanitizer report aborts the run
 // (-fno-sanitize-recover).
@@ -30,6 +30,11 @@ int64_t soc_debug_plan_frame(soc_renderer* r, const soc_globals* g, int32_t phas
 int64_t soc_debug_plan_clouds(const soc_globals* g, soc_img depth, soc_img noise, soc_img target, void* workspace,
                               int32_t sky_bound, const int32_t residency[6], void* state, char* buf, size_t cap);
 size_t soc_debug_cloud_state_bytes(void);
+// test hook of the Composition planner (csrc/composition_plan.cpp), not in the public header
+int64_t soc_debug_plan_composition(const soc_globals* g, const soc_globals* d_globals, const soc_img* images, uint32_t what,
+                                   soc_auto_exposure* ae, uint32_t* scratch, const soc_img* mip1, const soc_img* mip3,
+                                   const void* d_bounds, uint32_t light_flags, uint32_t* d_shaded,
+                                   const soc_sun_cascades* cascades, char* buf, size_t cap);
 }
 
 namespace {
@@ -281,6 +286,108 @@ void clouds_plan(const soc_globals& g0, int W, int H) {
            "clouds plan: null residency");
     g.resolution[0] = 0;
     expect(soc_debug_plan_clouds(&g, depth, noise, target, ws, 0, res, nullptr, buf, sizeof buf) == 0, "clouds plan: empty extent");
+}
+
+// The Composition planner through its test hook (no GPU call; fake, never dereferenced addresses): each entry point's
+// call on the pair and the generic path, the render graph's forms, SkyCompose, each rejection, a truncated buffer and the
+// length-only call.
+void composition_plan(const soc_globals& g0) {
+    enum { HIST = 1, FOLD = 2, SKY_EXTERNAL = 4, BOUNDED = 8, CASCADED = 16, SKY_COMPOSE = 32 };
+    char* fake = reinterpret_cast<char*>(0x10000000);
+    const int S = 256;
+    soc_globals g = g0;
+    soc_sun_cascades rec;
+    expect(soc_sun_cascades_from_sun(&g, S, &rec) == SOC_OK, "composition plan: a one-cascade record");
+    auto* dg = reinterpret_cast<const soc_globals*>(fake + 0xa0000000u);
+    auto* ae = reinterpret_cast<soc_auto_exposure*>(fake + 0xb0000000u);
+    auto* scratch = reinterpret_cast<uint32_t*>(fake + 0xb1000000u);
+    auto* counter = reinterpret_cast<uint32_t*>(fake + 0xb2000000u);
+    const void* bounds = fake + 0xb3000000u;
+    char buf[2048];
+    struct Frame {
+        soc_img im[8], mip1, mip3;
+    };
+    auto frame = [&](int W, int H) {
+        Frame f;
+        const int fmt[8] = {SOC_FMT_RGBA16F, SOC_FMT_RGBA16F, SOC_FMT_RGBA16F, SOC_FMT_RGBA16F, SOC_FMT_D32F, SOC_FMT_R8_UNORM,
+                            SOC_FMT_D32F, SOC_FMT_RGBA8_UNORM};
+        const int bpp[8] = {8, 8, 8, 8, 4, 1, 4, 4};
+        for (int i = 0; i < 8; ++i) {
+            const int w = i == 5 ? (W + 1) / 2 : i == 6 ? S : W, h = i == 5 ? (H + 1) / 2 : i == 6 ? S : H;
+            f.im[i] = soc_img{fake + ((size_t)i << 28), w, h, w * bpp[i], fmt[i]};
+        }
+        f.mip1 = soc_img{fake + (8u << 28), W / 2, H / 2, W / 2 * 8, SOC_FMT_RGBA16F};
+        f.mip3 = soc_img{fake + 0x90000000u, W / 8, H / 8, W / 8 * 8, SOC_FMT_RGBA16F};
+        return f;
+    };
+    auto plan = [&](const Frame& f, uint32_t what, uint32_t flags = 0, uint32_t* n = nullptr, const soc_img* m1 = nullptr,
+                    const soc_img* m3 = nullptr, const soc_sun_cascades* cs = nullptr) {
+        return soc_debug_plan_composition(&g, dg, f.im, what, ae, scratch, m1, m3, bounds, flags, n, cs, buf, sizeof buf);
+    };
+    auto has = [&](const char* text) { return std::strstr(buf, text) != nullptr; };
+    g.point_light_count = 3;
+    g.spot_light_count = 2;
+    for (int pair = 1; pair >= 0; --pair) {
+        const Frame f = pair ? frame(64, 48) : frame(97, 55);
+        g.resolution[0] = f.im[0].width;
+        g.resolution[1] = f.im[0].height;
+        const char* path = pair ? "composition\tpair\t" : "composition\tgeneric\t";
+        expect(plan(f, 0) > 0 && has(path), "composition plan: soc_composition");
+        expect(plan(f, BOUNDED, SOC_LIGHTS_CULL, counter) > 0 && has(pair ? " lb=7 " : "composition_generic_bounded"),
+               "composition plan: soc_composition_bounded");
+        expect(plan(f, CASCADED, 0, nullptr, nullptr, nullptr, &rec) > 0 && has(pair ? " cs=1\t" : "composition_generic_cascaded"),
+               "composition plan: soc_composition_cascaded");
+        expect(plan(f, HIST | FOLD) > 0 && has(pair ? "histogram_fold" : "pass\tgenerate_luminance_histogram"),
+               "composition plan: soc_composition_luminance_histogram");
+        expect(plan(f, HIST | FOLD | BOUNDED) > 0 && has(pair ? " lb=1 " : "pass\t"),
+               "composition plan: soc_composition_luminance_histogram_bounded");
+        expect(plan(f, HIST | FOLD | CASCADED, 0, nullptr, nullptr, nullptr, &rec) > 0 && has("\tcascades=1,256:"),
+               "composition plan: soc_composition_luminance_histogram_cascaded");
+        // 97 clouds texels a row are no multiple of 8 bytes: the per-pixel form
+        expect(plan(f, SKY_COMPOSE) > 0 && has(pair ? "sky_compose_pair\tcp=1" : "sky_compose_pair\tcp=0"), "composition plan: SkyCompose");
+        if (pair) {   // the render graph's forms
+            expect(plan(f, HIST | SKY_EXTERNAL | BOUNDED, SOC_LIGHTS_CULL, nullptr, &f.mip1, &f.mip3) > 0 &&
+                       has(" bl=1 sp=1 lb=3 ") && !has("histogram_fold"), "composition plan: the render graph's call");
+            expect(plan(f, HIST | BOUNDED, 0, counter, &f.mip1) == SOC_E_INVALID_ARG, "composition plan: the counter with the in-kernel bloom");
+            expect(plan(f, HIST | CASCADED, 0, nullptr, &f.mip1, nullptr, &rec) == SOC_E_UNSUPPORTED, "composition plan: cascades with mip1");
+            expect(plan(f, HIST | CASCADED, 0, nullptr, nullptr, &f.mip3, &rec) == SOC_E_UNSUPPORTED, "composition plan: cascades with mip3");
+            expect(plan(f, HIST, 0, nullptr, &f.im[0]) == SOC_E_SHAPE, "composition plan: mip1 extent");
+            expect(plan(f, HIST, 0, nullptr, nullptr, &f.im[0]) == SOC_E_SHAPE, "composition plan: mip3 extent");
+            expect(plan(f, 0, 0, nullptr, &f.mip1) == SOC_E_SHAPE, "composition plan: mip1 without the histogram");
+        } else {      // the three errors after a failed fusion
+            expect(plan(f, HIST, 0, nullptr, nullptr, &f.mip3) == SOC_E_SHAPE, "composition plan: zero cells off the pair path");
+            expect(plan(f, HIST, 0, nullptr, &f.mip1) == SOC_E_SHAPE, "composition plan: in-kernel bloom off the pair path");
+            expect(plan(f, HIST | SKY_EXTERNAL) == SOC_E_INVALID_ARG, "composition plan: sky_external off the pair path");
+        }
+        expect(plan(f, SKY_EXTERNAL) == SOC_E_INVALID_ARG, "composition plan: sky_external without the histogram");
+        expect(plan(f, BOUNDED, 2) == SOC_E_INVALID_ARG, "composition plan: unknown flags");
+        expect(plan(f, CASCADED | BOUNDED, 0, nullptr, nullptr, nullptr, &rec) == SOC_E_UNSUPPORTED, "composition plan: cascades with bounds");
+        expect(plan(f, CASCADED) == SOC_E_INVALID_ARG, "composition plan: null cascades");
+        soc_sun_cascades bad = rec;
+        bad.count = 5;
+        expect(plan(f, CASCADED, 0, nullptr, nullptr, nullptr, &bad) == SOC_E_INVALID_ARG, "composition plan: cascades count");
+        for (int i = 0; i < 8; ++i) {
+            Frame b = f;
+            b.im[i].format = i == 4 || i == 6 ? SOC_FMT_RGBA16F : SOC_FMT_D32F;
+            expect(plan(b, HIST | FOLD) == SOC_E_INVALID_ARG, "composition plan: an image's format");
+        }
+        expect(soc_debug_plan_composition(&g, dg, f.im, 0, ae, scratch, nullptr, nullptr, bounds, 0, nullptr, nullptr, buf, 16) > 16 &&
+                   std::strlen(buf) == 15, "composition plan: truncated");
+        expect(soc_debug_plan_composition(&g, dg, f.im, HIST, ae, scratch, nullptr, nullptr, bounds, 0, nullptr, nullptr, nullptr, 0) > 0,
+               "composition plan: length only");
+        expect(soc_debug_plan_composition(&g, nullptr, f.im, 0, ae, scratch, nullptr, nullptr, bounds, 0, nullptr, nullptr, buf, sizeof buf) ==
+                   SOC_E_INVALID_ARG, "composition plan: lights without device globals");
+        expect(soc_debug_plan_composition(&g, dg, f.im, BOUNDED, ae, scratch, nullptr, nullptr, nullptr, 0, nullptr, nullptr, buf, sizeof buf) ==
+                   SOC_E_INVALID_ARG, "composition plan: bounded without bounds");
+        expect(soc_debug_plan_composition(nullptr, dg, f.im, 0, ae, scratch, nullptr, nullptr, bounds, 0, nullptr, nullptr, buf, sizeof buf) ==
+                   SOC_E_INVALID_ARG, "composition plan: null globals");
+        expect(soc_debug_plan_composition(&g, dg, f.im, HIST, nullptr, scratch, nullptr, nullptr, bounds, 0, nullptr, nullptr, buf, sizeof buf) ==
+                   SOC_E_INVALID_ARG, "composition plan: null auto exposure");
+        expect(soc_debug_plan_composition(&g, dg, f.im, SKY_COMPOSE, ae, nullptr, nullptr, nullptr, bounds, 0, nullptr, nullptr, buf, sizeof buf) ==
+                   SOC_E_INVALID_ARG, "composition plan: SkyCompose without scratch");
+        expect(soc_debug_plan_composition(&g, dg, nullptr, 0, ae, scratch, nullptr, nullptr, bounds, 0, nullptr, nullptr, buf, sizeof buf) ==
+                   SOC_E_INVALID_ARG, "composition plan: null images");
+    }
 }
 
 void writers(int W, int H) {
@@ -576,6 +683,7 @@ int main() {
         abi_introspection();
         render_graph(g, W, H);
         clouds_plan(g, W, H);
+        composition_plan(g);
         writers(W, H);
         oracle_frame(g, W, H);
         oracle_raster(g, W, H);
