@@ -367,6 +367,8 @@ DEBUG_FUNCTIONS = {
     "soc_debug_cloud_state_bytes": (C.c_size_t, []),
     "soc_debug_plan_composition": (C.c_int64, [_G, _P, C.POINTER(_IMG), C.c_uint32, _P, _P, C.POINTER(_IMG), C.POINTER(_IMG), _P,
                                                C.c_uint32, _P, C.POINTER(SunCascades), C.c_char_p, C.c_size_t]),
+    "soc_debug_plan_post": (C.c_int64, [C.c_int32, _G, C.POINTER(_IMG), C.c_int32, _P, C.c_int32, C.POINTER(C.c_int32), C.c_char_p,
+                                        C.c_size_t]),
     "soc_debug_bloom_zero_cell_footprint": (None, [C.c_int32] * 4 + [C.POINTER(C.c_int32)]),
 }
 

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "bloom_common.hpp"
+#include "post_plan.hpp"
 
 namespace soc {
 
@@ -248,107 +249,60 @@ __global__ __launch_bounds__(kWorkgroup) void bloom_up_double_q(DImg src, DImg d
     store_quad_row(dst, X0, Y0 + 1, out[1], vec);
 }
 
-constexpr int kFastMax = 8192;
-
-// Below this many output pixels the 1:2 upsample runs one pixel per lane (4x the lanes of the quad
-// kernel: small mips need the parallelism more than the shared window). Tuning knob:
-// SOC_BLOOM_QUAD_MIN_PX overrides it.
-long quad_min_px() {
-    static const long v = [] {
-        const char* e = getenv("SOC_BLOOM_QUAD_MIN_PX");
-        return e ? atol(e) : 1L << 20;
-    }();
-    return v;
-}
-
-bool vec16(const soc_img& im) { return im.pitch_bytes % 16 == 0 && reinterpret_cast<uintptr_t>(im.data) % 16 == 0; }
-
 }  // namespace
 
-int launch_bloom_down(const soc_img& hi, const soc_img& lo, hipStream_t s, int force_generic) {
-    dim3 blk(BX, BY), grd(ceil_div(lo.width, BX), ceil_div(lo.height, BY));
-    DImg src = dimg(hi), dst = dimg(lo);
-    const bool small = hi.width <= kFastMax && hi.height <= kFastMax;
-    if (!force_generic && small && hi.width == lo.width && hi.height == lo.height) {
-        dim3 g2(ceil_div(ceil_div(lo.width, 2), BX), ceil_div(ceil_div(lo.height, 2), BY));
-        launch("bloom_down_same_q", kWorkgroup, bloom_down_same_q, g2, blk, 0, s, src, dst, vec16(lo));
-    } else if (!force_generic && small && hi.width == 2 * lo.width && hi.height == 2 * lo.height) {
-        launch("bloom_down_half_w", kWorkgroup, bloom_down_half_w, grd, blk, 0, s, src, dst);
-    } else {
-        launch("bloom_down_generic", kWorkgroup, bloom_down_generic, grd, blk, 0, s, src, dst, 1.0f / (float)hi.width, 1.0f / (float)hi.height);
+// The plan's kernel on `s`: each instantiation is named here once; a form without an entry is SOC_E_INVALID_ARG.
+int issue_bloom_pass(const BloomPassPlan& pl, hipStream_t s) {
+    static_assert(BX == kBloomBX && BY == kBloomBY, "the planner's grids are in these blocks");
+    const dim3 blk(BX, BY), grd(pl.grid_x, pl.grid_y);
+    const bool up = pl.kernel >= kBloomUpSameQ;
+    switch (pl.kernel) {
+    case kBloomDownSameQ: launch("bloom_down_same_q", kWorkgroup, bloom_down_same_q, grd, blk, 0, s, pl.src, pl.dst, pl.vec); break;
+    case kBloomDownHalfW: launch("bloom_down_half_w", kWorkgroup, bloom_down_half_w, grd, blk, 0, s, pl.src, pl.dst); break;
+    case kBloomDownGeneric: launch("bloom_down_generic", kWorkgroup, bloom_down_generic, grd, blk, 0, s, pl.src, pl.dst, pl.tx, pl.ty); break;
+    case kBloomUpSameQ: launch("bloom_up_same_q", kWorkgroup, bloom_up_same_q, grd, blk, 0, s, pl.src, pl.dst, pl.vec); break;
+    case kBloomUpDouble: launch("bloom_up_double", kWorkgroup, bloom_up_double, grd, blk, 0, s, pl.src, pl.dst); break;
+    case kBloomUpDoubleQ: launch("bloom_up_double_q", kWorkgroup, bloom_up_double_q, grd, blk, 0, s, pl.src, pl.dst, pl.vec); break;
+    case kBloomUpGeneric: launch("bloom_up_generic", kWorkgroup, bloom_up_generic, grd, blk, 0, s, pl.src, pl.dst, pl.tx, pl.ty); break;
+    default: return set_error(SOC_E_INVALID_ARG, "bloom: no kernel of form %d", (int)pl.kernel);
     }
-    return check_launch("bloom_downsample");
-}
-
-int launch_bloom_up(const soc_img& lo, const soc_img& hi, hipStream_t s, int force_generic) {
-    dim3 blk(BX, BY), grd(ceil_div(hi.width, BX), ceil_div(hi.height, BY));
-    DImg src = dimg(lo), dst = dimg(hi);
-    const bool small = hi.width <= kFastMax && hi.height <= kFastMax;
-    if (!force_generic && small && hi.width == lo.width && hi.height == lo.height) {
-        dim3 g2(ceil_div(ceil_div(hi.width, 2), BX), ceil_div(ceil_div(hi.height, 2), BY));
-        launch("bloom_up_same_q", kWorkgroup, bloom_up_same_q, g2, blk, 0, s, src, dst, vec16(hi));
-    } else if (!force_generic && small && hi.width == 2 * lo.width && hi.height == 2 * lo.height) {
-        if ((long)hi.width * hi.height < quad_min_px()) {
-            launch("bloom_up_double", kWorkgroup, bloom_up_double, grd, blk, 0, s, src, dst);
-        } else {
-            dim3 g2(ceil_div(lo.width, BX), ceil_div(lo.height, BY));
-            launch("bloom_up_double_q", kWorkgroup, bloom_up_double_q, g2, blk, 0, s, src, dst, vec16(hi));
-        }
-    } else {
-        launch("bloom_up_generic", kWorkgroup, bloom_up_generic, grd, blk, 0, s, src, dst, 1.0f / (float)lo.width, 1.0f / (float)lo.height);
-    }
-    return check_launch("bloom_upsample");
+    return check_launch(up ? "bloom_upsample" : "bloom_downsample");
 }
 
 }  // namespace soc
 
 using namespace soc;
 
-static int bloom_args(const soc_img& a, const soc_img& b, const char* pass) {
-    int rc = check_img(a, SOC_FMT_RGBA16F, pass, "source");
+// up: a is the lower mip; force_generic: soc_debug_bloom_generic
+static int bloom_pass(bool up, const soc_img& a, const soc_img& b, const char* pass, bool force_generic, soc_stream stream) {
+    const int rc = bloom_args(a, b, pass);
     if (rc) return rc;
-    rc = check_img(b, SOC_FMT_RGBA16F, pass, "target");
-    if (rc) return rc;
-    if (a.data == b.data) return set_error(SOC_E_INVALID_ARG, "%s: source and target alias", pass);
-    return SOC_OK;
+    BloomPassPlan pl;
+    if (up) plan_bloom_up(a, b, force_generic, pl);
+    else plan_bloom_down(a, b, force_generic, pl);
+    return issue_bloom_pass(pl, hs(stream));
 }
 
 extern "C" int soc_bloom_downsample(const soc_globals* g, soc_img higher_mip, soc_img lower_mip, soc_stream stream) {
     (void)g;
-    int rc = bloom_args(higher_mip, lower_mip, "soc_bloom_downsample");
-    if (rc) return rc;
-    return launch_bloom_down(higher_mip, lower_mip, hs(stream), 0);
+    return bloom_pass(false, higher_mip, lower_mip, "soc_bloom_downsample", false, stream);
 }
 
 extern "C" int soc_bloom_upsample(const soc_globals* g, soc_img lower_mip, soc_img higher_mip, soc_stream stream) {
     (void)g;
-    int rc = bloom_args(lower_mip, higher_mip, "soc_bloom_upsample");
-    if (rc) return rc;
-    return launch_bloom_up(lower_mip, higher_mip, hs(stream), 0);
+    return bloom_pass(true, lower_mip, higher_mip, "soc_bloom_upsample", false, stream);
 }
 
 // Test hook: force the generic (float-uv) tap path to cross-check the fast paths.
 extern "C" int soc_debug_bloom_generic(int32_t up, soc_img a, soc_img b, soc_stream stream) {
-    int rc = bloom_args(a, b, "soc_debug_bloom_generic");
-    if (rc) return rc;
-    return up ? launch_bloom_up(a, b, hs(stream), 1) : launch_bloom_down(a, b, hs(stream), 1);
+    return bloom_pass(up != 0, a, b, "soc_debug_bloom_generic", true, stream);
 }
 
 extern "C" int soc_bloom_weighted_stage(const soc_globals* g, soc_img emissive, const soc_img* mips, int32_t mip_count,
                                         soc_img output, int32_t stage, soc_stream stream) {
     (void)g;
-    static const char* P = "soc_bloom_weighted_stage";
-    if (!mips) return set_error(SOC_E_INVALID_ARG, "%s: null mips", P);
-    if (stage < 0 || stage > 4) return set_error(SOC_E_INVALID_ARG, "%s: stage %d not in 0..4", P, stage);
-    int rc = check_img(emissive, SOC_FMT_RGBA16F, P, "emissive");
-    if (!rc) rc = check_img(output, SOC_FMT_RGBA16F, P, "output");
-    for (int i = 0; !rc && i < mip_count; ++i) rc = check_img(mips[i], SOC_FMT_RGBA16F, P, "mip");
-    if (rc) return rc;
-    if (!bloom_fused_applicable(emissive, mips, mip_count, output))
-        return set_error(SOC_E_UNSUPPORTED, "%s: needs 4 mips halving exactly from the emissive extent (<= 8192)", P);
-    if ((stage == 0 || stage == 4) && output.data == mips[1].data)
-        return set_error(SOC_E_INVALID_ARG, "%s: output aliases mip 1", P);
-    return launch_bloom_weighted(emissive, mips, output, hs(stream), stage);
+    const int rc = check_bloom_weighted_stage(emissive, mips, mip_count, output, stage);
+    return rc ? rc : bloom_weighted(emissive, mips, output, hs(stream), stage);
 }
 
 extern "C" int soc_bloom_chain(const soc_globals* g, soc_img emissive, const soc_img* mips, int32_t mip_count,

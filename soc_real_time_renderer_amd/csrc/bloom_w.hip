@@ -19,28 +19,7 @@
 // contents are unobservable in the reference graph. An intermediate tile entry at an out-of-image
 // coordinate holds the value of the clamped coordinate, which is what the next pass's clamped taps read.
 #include "bloom_w.hpp"
-
-namespace soc {
-// The chain's fixed-ratio fast paths apply when the four mips halve exactly (the reference's mip chain at even
-// extents, renderer.cpp:492-513) and the extents fit the 8-bit fixed-point tap range.
-bool bloom_fused_applicable(const soc_img& emissive, const soc_img* mips, int mip_count, const soc_img& output) {
-    if (mip_count != 4 || output.width != emissive.width || output.height != emissive.height) return false;
-    if (emissive.width > 8192 || emissive.height > 8192) return false;
-    if (mips[0].width != emissive.width || mips[0].height != emissive.height) return false;
-    for (int i = 1; i < 4; ++i)
-        if (mips[i - 1].width != 2 * mips[i].width || mips[i - 1].height != 2 * mips[i].height || mips[i].width < 2 ||
-            mips[i].height < 2)
-            return false;
-    return true;
-}
-
-// The last stage may leave proven-zero strips unwritten (launch_bloom_weighted's sparse_output): the register-form W4
-// with the zero skip, unless SOC_BLOOM_SPARSE=0 (the dense launches, for A/B).
-bool bloom_sparse_applicable() {
-    return tuning_knob("SOC_BLOOM_SPARSE", 1) != 0 && tuning_knob("SOC_BLOOM_ZERO_SKIP", 1) != 0 &&
-           tuning_knob("SOC_BLOOM_UP10_REG", 1) != 0;
-}
-}  // namespace soc
+#include "post_plan.hpp"
 
 // Test hook (no GPU needed): the mip3 footprint {x0, x1, y0, y1} (inclusive) of cell (a, b) for a w3 x h3 mip3.
 extern "C" void soc_debug_bloom_zero_cell_footprint(int32_t a, int32_t b, int32_t w3, int32_t h3, int32_t out[4]) {
@@ -147,7 +126,7 @@ __device__ __forceinline__ void up11_pair(const uint2 (*t)[TW], int cx, int cy, 
 // mode (tests/test_gpu_parity.py).
 template <int MODE>
 struct W1 {
-    static constexpr int OW = MODE ? 30 : 32, OH = MODE == 2 ? 16 : 8;   // mip1 outputs per workgroup
+    static constexpr int OW = w1_ow(MODE), OH = w1_oh(MODE);   // mip1 outputs per workgroup (30 or 32 x 8 or 16)
     static constexpr int MW = 2 * OW + 4, MH = 2 * OH + 4;  // mip0 tile, origin (2 X0 - 2, 2 Y0 - 2)
     static constexpr int EW = MW + 4, EH = MH + 4;          // emissive tile, origin (2 X0 - 4, 2 Y0 - 4)
     static constexpr int RUN = MH / 4;                      // mip0 entries per lane run (64 columns x 2 parities x 2 runs)
@@ -349,7 +328,6 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_down01p(DImg E, DImg M1, in
 // ================================================================================================
 // W2: mip1 -> [mip2, LDS] -> mip3
 // ================================================================================================
-constexpr int W2_OW = 16, W2_OH = 8;                          // mip3 outputs per workgroup
 constexpr int W2_MW = 2 * W2_OW + 4, W2_MH = 2 * W2_OH + 4;   // mip2 tile 36 x 20
 constexpr int W2_SW = 2 * W2_MW + 4, W2_SH = 2 * W2_MH + 4;   // mip1 tile 76 x 44
 
@@ -424,7 +402,6 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_down23(DImg S1, DImg M3, in
 // ================================================================================================
 // W3: mip3 -> [mip2, LDS] -> mip1 (64 x 16 mip1 outputs per workgroup)
 // ================================================================================================
-constexpr int U_OW = 64, U_OH = 16;
 constexpr int W3_MW = U_OW / 2 + 4, W3_MH = U_OH / 2 + 4;   // mip2 tile 36 x 12, origin (X0/2 - 2, Y0/2 - 2)
 constexpr int W3_SW = W3_MW / 2 + 4, W3_SH = W3_MH / 2 + 4; // mip3 tile 22 x 10, origin (X0/4 - 3, Y0/4 - 3)
 
@@ -664,10 +641,6 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_up10s(DImg S1, DImg O, bool
 // Up10Tile (bloomw_up10s), so the same bits, without its four LDS phases (~180 B of LDS traffic per output pixel). Alone
 // at C3 36.4-36.8 us against 38.3-39.3 for bloomw_up10s, in the frame within noise; 8 / 32 rows per wave and 64-column
 // aligned strips measured the same (the 66 MB output stream is what is left).
-#ifndef SOC_BLOOM_UP10_ROWS
-#define SOC_BLOOM_UP10_ROWS 16
-#endif
-constexpr int R_OW = 62, R_TH = SOC_BLOOM_UP10_ROWS;
 __device__ __forceinline__ uint32_t up_from_left(uint32_t v) {   // lane i <- lane i-1 (wave_shr:1)
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);
 }
@@ -798,85 +771,76 @@ __global__ __launch_bounds__(kWorkgroup) void bloomw_up10r(DImg S1, DImg O, int 
     }
 }
 
-// Workgroups of 256 lanes of bloomw_down01p resident on the whole device at once (the persistent kernel's grid bound),
-// queried once per device and cached (the occupancy query is not on the per-frame enqueue path).
-template <int MODE, bool ZS>
-int down01p_resident_set() {
+void (*const kDown01p[3][2])(DImg, DImg, int, int) = {{bloomw_down01p<0, false>, bloomw_down01p<0, true>},
+                                                      {bloomw_down01p<1, false>, bloomw_down01p<1, true>},
+                                                      {bloomw_down01p<2, false>, bloomw_down01p<2, true>}};
+
+// Workgroups of 256 lanes of bloomw_down01p<mode, zs> resident on the whole device at once (the persistent kernel's grid
+// bound), at [mode * 2 + zs]: queried once per device and cached (the occupancy query is not on the per-frame enqueue path).
+const int* down01p_resident_sets() {
     constexpr int kMaxDevices = 64;
-    static int cached[kMaxDevices] = {};
-    int dev = 0, cus = 256, per = 0;
+    static int cached[kMaxDevices + 1][6] = {};
+    int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < kMaxDevices && cached[dev]) return cached[dev];
+    int* set = cached[dev >= 0 && dev < kMaxDevices ? dev : kMaxDevices];   // the last row: never kept
+    if (set[0] && set != cached[kMaxDevices]) return set;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, bloomw_down01p<MODE, ZS>, 256, 0);
-    const int n = std::max(per, 1) * cus;
-    if (dev >= 0 && dev < kMaxDevices) cached[dev] = n;
-    return n;
+    for (int i = 0; i < 6; ++i) {
+        int per = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kDown01p[i / 2][i % 2], 256, 0);
+        set[i] = std::max(per, 1) * cus;
+    }
+    return set;
 }
 
-bool a16(const soc_img& im) { return im.pitch_bytes % 16 == 0 && reinterpret_cast<uintptr_t>(im.data) % 16 == 0; }
+// The plan's kernels on `s`, in order: each instantiation is named here once; a form without an entry is SOC_E_INVALID_ARG.
+int issue_bloom_weighted(const BloomwPlan& pl, hipStream_t s) {
+    static void (*const down23[2])(DImg, DImg, int, int, int) = {bloomw_down23<false>, bloomw_down23<true>};
+    static void (*const up32s[2])(DImg, DImg, int, int, bool, int) = {bloomw_up32s<false>, bloomw_up32s<true>};
+    static void (*const up10r[2][2])(DImg, DImg, int, int, DImg) = {{bloomw_up10r<false>, nullptr}, {bloomw_up10r<true>, bloomw_up10r<true, true>}};
+    for (int i = 0; i < pl.n; ++i) {
+        const BloomwStage& st = pl.st[i];
+        const dim3 g(st.grid_x, st.grid_y);
+        const int* a = st.a;
+        const bool f01 = (st.f0 == 0 || st.f0 == 1) && (st.f1 == 0 || st.f1 == 1);
+        switch (st.kernel) {
+        case kBwDown01p:
+            if (st.f0 < 0 || st.f0 > 2 || (st.f1 != 0 && st.f1 != 1)) break;
+            launch("bloomw_down01p", kWorkgroup, kDown01p[st.f0][st.f1], g, kWorkgroup, 0, s, st.src, st.dst, a[0], a[1]);
+            continue;
+        case kBwDown23:
+            if (!f01) break;
+            launch("bloomw_down23", kWorkgroup, down23[st.f0], g, kWorkgroup, 0, s, st.src, st.dst, a[0], a[1], a[2]);
+            continue;
+        case kBwUp32s:
+            if (!f01) break;
+            launch("bloomw_up32s", kWorkgroup, up32s[st.f0], g, kWorkgroup, 0, s, st.src, st.dst, a[0], a[1], a[2] != 0, a[3]);
+            continue;
+        case kBwUp32:
+            launch("bloomw_up32", kWorkgroup, bloomw_up32, g, kWorkgroup, 0, s, st.src, st.dst, a[0], a[1], a[2] != 0, a[3]);
+            continue;
+        case kBwUp10r:
+            if (!f01 || !up10r[st.f0][st.f1]) break;
+            launch("bloomw_up10r", kWorkgroup, up10r[st.f0][st.f1], g, kWorkgroup, 0, s, st.src, st.dst, a[0], a[1], st.m3);
+            continue;
+        case kBwUp10s:
+            launch("bloomw_up10s", kWorkgroup, bloomw_up10s, g, kWorkgroup, 0, s, st.src, st.dst, a[0] != 0, a[1], a[2] != 0);
+            continue;
+        case kBwUp10:
+            launch("bloomw_up10", kWorkgroup, bloomw_up10, g, kWorkgroup, 0, s, st.src, st.dst, a[0] != 0, a[1]);
+            continue;
+        }
+        return set_error(SOC_E_INVALID_ARG, "bloom_weighted: no kernel of form %d <%d, %d>", (int)st.kernel, st.f0, st.f1);
+    }
+    return check_launch("bloom_weighted");
+}
 
 }  // namespace
 
-int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage,
-                          bool sparse_output) {
-    const DImg E = dimg(emissive), M1 = dimg(mips[1]), M3 = dimg(mips[3]), O = dimg(output);
-    const int swz = 1;   // XCD-aware order: halo re-reads served by L2 (2.0x -> 1.0x HBM traffic)
-    // all-zero tiles / rows skip their filters (bloomw_down01p, bloomw_up10r): 0 = every tile filtered, the same bits
-    const bool zero_skip = tuning_knob("SOC_BLOOM_ZERO_SKIP", 1) != 0;
-    if (stage == 0 || stage == 1) {
-        // persistent: one resident set of workgroups (a multiple of 8, so a workgroup's tiles stay on its XCD)
-        auto w1 = [&](auto mode, auto zs) {
-            constexpr int R = decltype(mode)::value;
-            constexpr bool Z = decltype(zs)::value;
-            const int ntx = ceil_div(mips[1].width, W1<R>::OW), nty = ceil_div(mips[1].height, W1<R>::OH);
-            const int grid = std::max(8, (std::min(ntx * nty, down01p_resident_set<R, Z>()) / 8) * 8);
-            launch("bloomw_down01p", kWorkgroup, bloomw_down01p<R, Z>, grid, kWorkgroup, 0, s, E, M1, ntx, nty);
-        };
-        auto w1z = [&](auto mode) {
-            if (zero_skip) w1(mode, std::true_type{});
-            else w1(mode, std::false_type{});
-        };
-        const int mode = tuning_knob("SOC_BLOOM_W1_REG", 1);
-        if (mode == 2) w1z(std::integral_constant<int, 2>{});
-        else if (mode == 1) w1z(std::integral_constant<int, 1>{});
-        else w1z(std::integral_constant<int, 0>{});
-    }
-    if (stage == 0 || stage == 2) {
-        dim3 g(ceil_div(mips[3].width, W2_OW), ceil_div(mips[3].height, W2_OH));
-        if (tuning_knob("SOC_BLOOM_W2_REG", 1))
-            launch("bloomw_down23", kWorkgroup, bloomw_down23<true>, g, kWorkgroup, 0, s, M1, M3, mips[2].width, mips[2].height, swz);
-        else
-            launch("bloomw_down23", kWorkgroup, bloomw_down23<false>, g, kWorkgroup, 0, s, M1, M3, mips[2].width, mips[2].height, swz);
-    }
-    if (stage == 0 || stage == 3) {
-        dim3 g(ceil_div(mips[1].width, U_OW), ceil_div(mips[1].height, U_OH));
-        if (tuning_knob("SOC_BLOOM_UP_SEP", 1))
-            if (tuning_knob("SOC_BLOOM_W3_RUNS", 1))
-                launch("bloomw_up32s", kWorkgroup, bloomw_up32s<true>, g, kWorkgroup, 0, s, M3, M1, mips[2].width, mips[2].height, a16(mips[1]), swz);
-            else
-                launch("bloomw_up32s", kWorkgroup, bloomw_up32s<false>, g, kWorkgroup, 0, s, M3, M1, mips[2].width, mips[2].height, a16(mips[1]), swz);
-        else
-            launch("bloomw_up32", kWorkgroup, bloomw_up32, g, kWorkgroup, 0, s, M3, M1, mips[2].width, mips[2].height, a16(mips[1]), swz);
-    }
-    if (stage == 0 || stage == 4) {
-        dim3 g(ceil_div(output.width, U_OW), ceil_div(output.height, U_OH));
-        if (sparse_output && !bloom_sparse_applicable())
-            return set_error(SOC_E_INVALID_ARG, "bloom_weighted: the sparse output needs the register-form last stage and the zero skip");
-        if (tuning_knob("SOC_BLOOM_UP10_REG", 1)) {
-            const int nwx = ceil_div(output.width, R_OW), nwaves = nwx * ceil_div(output.height, R_TH);
-            if (sparse_output)   // proven-zero strips store nothing (bloom_sparse_applicable held: zero_skip and this form)
-                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<true, true>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves, M3);
-            else if (zero_skip)
-                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<true>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves, M3);
-            else
-                launch("bloomw_up10r", kWorkgroup, bloomw_up10r<false>, ceil_div(nwaves, kWorkgroup / 64), kWorkgroup, 0, s, M1, O, nwx, nwaves, M3);
-        } else if (tuning_knob("SOC_BLOOM_UP_SEP", 1))
-            launch("bloomw_up10s", kWorkgroup, bloomw_up10s, g, kWorkgroup, 0, s, M1, O, a16(output), swz, zero_skip);
-        else
-            launch("bloomw_up10", kWorkgroup, bloomw_up10, g, kWorkgroup, 0, s, M1, O, a16(output), swz);
-    }
-    return check_launch("bloom_weighted");
+int bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage, bool sparse_output) {
+    BloomwPlan pl;
+    const int rc = plan_bloom_weighted(emissive, mips, output, stage, sparse_output, stage <= 1 ? down01p_resident_sets() : nullptr, pl);
+    return rc ? rc : issue_bloom_weighted(pl, s);
 }
 
 }  // namespace soc

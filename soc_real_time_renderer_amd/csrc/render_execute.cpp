@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "post_plan.hpp"
 #include "renderer.hpp"
 
 using namespace soc;

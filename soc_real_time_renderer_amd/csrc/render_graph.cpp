@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "composition_plan.hpp"
+#include "post_plan.hpp"
 #include "renderer.hpp"
 
 using namespace soc;
@@ -204,7 +205,7 @@ void build_passes(soc_renderer* r) {
                 const soc_img& dst = r->bloom_image();
                 // SOC_BLOOM_SPARSE: strips proven zero from mip3 are left unwritten; Composition proves the same cells
                 if (st == 4 && r->bloom_sparse_frame)
-                    return soc::launch_bloom_weighted(r->img.emissive, r->img.bloom_mips, dst, s, 4, true);
+                    return soc::bloom_weighted(r->img.emissive, r->img.bloom_mips, dst, s, 4, true);
                 return soc_bloom_weighted_stage(g, r->img.emissive, r->img.bloom_mips, 4, dst, st, (soc_stream)s);
             });
         return;

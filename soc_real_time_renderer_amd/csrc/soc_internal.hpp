@@ -37,6 +37,15 @@ inline bool img_ok(const soc_img& im) {
 // Validates `im` (and its format when fmt > 0); sets the error string on failure.
 int check_img(const soc_img& im, int fmt, const char* pass, const char* what);
 
+// Base address and pitch are multiples of n bytes (a power of two): rows take n-byte loads and stores.
+inline bool aligned_to(const soc_img& im, unsigned n) {
+    return (reinterpret_cast<uintptr_t>(im.data) & (n - 1)) == 0 && ((unsigned)im.pitch_bytes & (n - 1)) == 0;
+}
+// The image fits a buffer resource's 32-bit offsets (a signed 24-bit row x pitch product).
+inline bool buffer_range_ok(const soc_img& im) {
+    return (long long)im.pitch_bytes * im.height < (1ll << 31) && im.pitch_bytes < (1 << 23);
+}
+
 inline DImg dimg(const soc_img& im) { return DImg{static_cast<char*>(im.data), im.width, im.height, im.pitch_bytes}; }
 
 inline Mat4 mat4(const float* m) {
@@ -85,15 +94,6 @@ inline unsigned ceil_div(unsigned a, unsigned b) { return (a + b - 1) / b; }
 // float code: compiled without FMA contraction).
 void agx_matrices(float compression, float M[9], float Minv[9]);
 void mat4_mul_host(float out[16], const float a[16], const float b[16]);
-
-// The bloom chain's exactly-halving mips (bloom_w.hip).
-bool bloom_fused_applicable(const soc_img& emissive, const soc_img* mips, int mip_count, const soc_img& output);
-// Weighted-form bloom chain (bloom_w.hip): same applicability as the fused chain.
-// sparse_output (the render graph's last stage under SOC_BLOOM_SPARSE, when bloom_sparse_applicable()): output strips
-// proven zero from mips[3] are not written; the reader must take the constant there (composition's bloom_mip3).
-int launch_bloom_weighted(const soc_img& emissive, const soc_img* mips, const soc_img& output, hipStream_t s, int stage,
-                          bool sparse_output = false);
-bool bloom_sparse_applicable();
 
 // The device record of a frame's light ranges (soc_upload_light_bounds writes it, composition.hip reads it; the library's
 // own layout, SOC_LIGHT_BOUNDS_DEVICE_BYTES): per light RN(1 / RN(r * r)) for the window (0: unlimited) and RN(r * r) for

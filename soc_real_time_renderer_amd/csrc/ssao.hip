@@ -8,27 +8,10 @@
 // a pure function of (uv, normal-image width): it is either evaluated inline or read from a table
 // filled once per resolution by the SAME device function (soc_ssao_prepare_noise), so both give
 // identical bits.
-#include "soc_internal.hpp"
+#include "post_plan.hpp"
 
 namespace soc {
 namespace {
-
-struct SsaoParams {
-    Mat4 inv_proj;
-    Mat4 proj;
-    Mat4 view;
-    float radius, bias, kernel_size_f;
-    int ksize;     // loop bound, min(kernel_size, 26)
-    int noise_w;   // textureSize(u_normal_image).x
-    int swz;       // XCD-aware tile order (tuning knob SOC_SWZ_SSAO, see xcd_order; 0 = row-major)
-    float rw, rh;  // recip_rn(target extent) for the pixel-centre uv (div_rn)
-    // host-folded constants of the tap loop (make_params): the projection rows x, y, w scaled to texel space
-    // (x 256 sub-texel steps on the sparse path), the texel-space centre and clamp bounds, 1 / kernel_size
-    float pa[3][4];
-    float c0x, c0y, tmx, tmy;
-    float inv_ksize;
-    float inv_radius;   // 1 / radius (the sparse path requires radius > 0)
-};
 
 // Deterministic sin / cos / pow of the noise (quirk Q8). The hash fract(sin(a) * 43758.5453) turns a 1-ulp difference of
 // sin into ~3e-3 of the hash, and the device's sinf and the host libm's round differently on ~1 in 2 arguments, so both
@@ -578,16 +561,10 @@ __device__ __forceinline__ void ssao_stage_tile(float4* tile4, __amdgpu_buffer_r
 
 // The default tile: 64 x 16 half-res pixels (1024 lanes), a 32-texel halo (tile sweep: profiles/r03_ssao_tile_sweep.txt);
 // kSsaoTileLanes is the launch bound its launcher checks.
-#ifndef SOC_SSAO_TILE_TX
-#define SOC_SSAO_TILE_TX 64   // A/B builds: the tile's half-res extent and halo
-#endif
-#ifndef SOC_SSAO_TILE_TY
-#define SOC_SSAO_TILE_TY 16
-#endif
 #ifndef SOC_SSAO_HALO
 #define SOC_SSAO_HALO 32
 #endif
-constexpr int kSsaoTX = SOC_SSAO_TILE_TX, kSsaoTY = SOC_SSAO_TILE_TY, kSsaoHalo = SOC_SSAO_HALO, kSsaoTileLanes = kSsaoTX * kSsaoTY;
+constexpr int kSsaoHalo = SOC_SSAO_HALO;   // the tile, kSsaoTX x kSsaoTY: post_plan.hpp
 
 // EARLY (tuning knob SOC_SSAO_EARLY): 2 (default) stages the tile with every load of a lane issued before its first LDS
 // store (ssao_stage_tile; the round-4 loop waited on each load in turn); 1 in addition fetches the pixel's normal texels
@@ -797,36 +774,23 @@ __global__ __launch_bounds__(kWorkgroup) void ssao_blur_generic(DImg src, DImg d
     row_ptr_w<uint8_t>(dst, y)[x] = (uint8_t)to_unorm8(result / 16.0f);
 }
 
-SsaoParams make_params(const soc_globals* g, const soc_img& normal) {
-    SsaoParams p;
-    p.inv_proj = mat4(g->camera_inverse_projection_matrix);
-    p.proj = mat4(g->camera_projection_matrix);
-    p.view = mat4(g->camera_view_matrix);
-    p.radius = g->ssao_radius;
-    p.bias = g->ssao_bias;
-    p.kernel_size_f = (float)g->ssao_kernel_size;
-    p.ksize = g->ssao_kernel_size < SOC_SSAO_MAX_KERNEL ? g->ssao_kernel_size : SOC_SSAO_MAX_KERNEL;
-    p.noise_w = normal.width;
-    p.swz = tuning_knob("SOC_SWZ_SSAO", -16);   // XCD vertical bands: HBM traffic 3.3x -> 1.25x algorithmic
-    p.inv_ksize = 1.0f / p.kernel_size_f;
-    p.inv_radius = 1.0f / p.radius;
-    return p;
-}
-
-// The tap loop's uniform constants for a depth image of W x H (sip: the sparse-inverse-projection path, whose x / y
-// forms count 1/256-texel steps with the rounding's +0.5 folded into the centre).
-void fold_tap_constants(SsaoParams& p, int W, int H, bool sip) {
-    const float fxs = sip ? 256.0f : 1.0f;
-    const float scale[3] = {0.5f * (float)W * fxs, 0.5f * (float)H * fxs, 1.0f};
-    const int rows[3] = {0, 1, 3};
-    for (int k = 0; k < 3; ++k)
-        for (int j = 0; j < 4; ++j) p.pa[k][j] = p.proj.m[4 * j + rows[k]] * scale[k];
-    const float cx0 = 0.5f * (float)(W - 1), cy0 = 0.5f * (float)(H - 1);
-    const float tmax_x = (float)(W - 1) - 1.0f / 256.0f, tmax_y = (float)(H - 1) - 1.0f / 256.0f;
-    p.c0x = sip ? cx0 * 256.0f + 0.5f : cx0;
-    p.c0y = sip ? cy0 * 256.0f + 0.5f : cy0;
-    p.tmx = sip ? tmax_x * 256.0f + 0.5f : tmax_x;
-    p.tmy = sip ? tmax_y * 256.0f + 0.5f : tmax_y;
+// The plan's kernel on `stream`: each instantiation is named here once; a form without an entry is SOC_E_INVALID_ARG.
+int issue_ssao(const SsaoPlan& pl, soc_stream stream) {
+    using K = void (*)(DImg, DImg, DImg, const float2*, SsaoParams);
+    static const K pipe[2] = {ssao_pipe_kernel<kSsaoTX, kSsaoTY, kSsaoHalo, false>, ssao_pipe_kernel<kSsaoTX, kSsaoTY, kSsaoHalo, true>};
+    static const K lds[3] = {ssao_lds_kernel<true, true, true, kSsaoTX, kSsaoTY, kSsaoHalo, 2, true>,
+                             ssao_lds_kernel<true, true, true, kSsaoTX, kSsaoTY, kSsaoHalo, 2, true, 1>,
+                             ssao_lds_kernel<true, true, true, kSsaoTX, kSsaoTY, kSsaoHalo, 2, true, 2>};
+    static const K gather[2][2][2] = {{{ssao_kernel<false, false, false>, nullptr}, {nullptr, ssao_kernel<false, true, true>}},
+                                      {{ssao_kernel<true, false, false>, nullptr}, {ssao_kernel<true, true, false>, ssao_kernel<true, true, true>}}};
+    const bool tile = pl.kernel == kSsaoPipe || pl.kernel == kSsaoLds;
+    const K k = pl.kernel == kSsaoPipe ? pipe[pl.persp]
+                : pl.kernel == kSsaoLds ? (pl.early >= 0 && pl.early <= 2 ? lds[pl.early] : nullptr)
+                : pl.kernel == kSsaoGather ? gather[pl.table][pl.sip][pl.full] : nullptr;
+    if (!k) return set_error(SOC_E_INVALID_ARG, "ssao_generation: no kernel of form %d", (int)pl.kernel);
+    launch(pl.kernel == kSsaoPipe ? "ssao_pipe_kernel" : tile ? "ssao_lds_kernel" : "ssao_kernel", tile ? kSsaoTileLanes : kWorkgroup, k,
+           dim3(pl.grid_x, pl.grid_y), dim3(pl.block_x), 0, hs(stream), pl.depth, pl.normal, pl.target, pl.noise, pl.p);
+    return check_launch("ssao_generation");
 }
 
 }  // namespace
@@ -835,9 +799,8 @@ void fold_tap_constants(SsaoParams& p, int W, int H, bool sip) {
 using namespace soc;
 
 extern "C" int soc_ssao_prepare_noise(soc_img normal, soc_img target, float* noise_table, soc_stream stream) {
-    if (!noise_table) return set_error(SOC_E_INVALID_ARG, "soc_ssao_prepare_noise: null table");
-    if (normal.width <= 0 || target.width <= 0 || target.height <= 0)
-        return set_error(SOC_E_INVALID_ARG, "soc_ssao_prepare_noise: bad extents");
+    const int rc = check_ssao_prepare_noise(normal, target, noise_table);
+    if (rc) return rc;
     dim3 blk(64, 4), grd(ceil_div(target.width, 64), ceil_div(target.height, 4));
     launch("ssao_noise_kernel", kWorkgroup, ssao_noise_kernel, grd, blk, 0, hs(stream), target.width, target.height, normal.width,
                                                    reinterpret_cast<float2*>(noise_table));
@@ -846,85 +809,18 @@ extern "C" int soc_ssao_prepare_noise(soc_img normal, soc_img target, float* noi
 
 extern "C" int soc_ssao_generation(const soc_globals* g, soc_img depth, soc_img normal, soc_img target,
                                    const float* noise_table, soc_stream stream) {
-    if (!g) return set_error(SOC_E_INVALID_ARG, "soc_ssao_generation: null globals");
-    int rc = check_img(depth, SOC_FMT_D32F, "soc_ssao_generation", "depth");
-    if (!rc) rc = check_img(normal, SOC_FMT_RGBA16F, "soc_ssao_generation", "normal");
-    if (!rc) rc = check_img(target, SOC_FMT_R8_UNORM, "soc_ssao_generation", "target");
-    if (rc) return rc;
-    if (depth.width < 2 || depth.height < 2)
-        return set_error(SOC_E_SHAPE, "soc_ssao_generation: depth must be at least 2x2");
-    if ((long long)depth.pitch_bytes * depth.height >= (1ll << 31) || depth.pitch_bytes >= (1 << 23))
-        return set_error(SOC_E_SHAPE, "soc_ssao_generation: depth image exceeds the 2 GiB buffer-offset range");
-    SsaoParams p = make_params(g, normal);
-    p.rw = recip_rn(target.width);
-    p.rh = recip_rn(target.height);
-    const float* IP = g->camera_inverse_projection_matrix;
-    // sparse inverse projection (the reference's perspective) whose w row stays positive over depths [-1, 1]
-    const bool sip = IP[2] == 0.0f && IP[3] == 0.0f && IP[6] == 0.0f && IP[7] == 0.0f && IP[15] - IP[11] > 0.0f &&
-                     IP[15] + IP[11] > 0.0f && p.radius > 0.0f && std::isfinite(p.inv_radius);
-    fold_tap_constants(p, depth.width, depth.height, sip);
-    const dim3 blk(256), grd(ceil_div(target.width, 32), ceil_div(target.height, 8));
-    const float2* tb = reinterpret_cast<const float2*>(noise_table);
-    hipStream_t st = hs(stream);
-    DImg dd = dimg(depth), dn = dimg(normal), dt = dimg(target);
-#define SOC_SSAO_LAUNCH(T, B, F) launch("ssao_kernel", kWorkgroup, ssao_kernel<T, B, F>, grd, blk, 0, st, dd, dn, dt, tb, p)
-    const bool full = p.ksize == SOC_SSAO_MAX_KERNEL;
-    // default: the LDS-tiled kernel (64 x 16 pixels, 32-texel halo) in the contiguous-eighths XCD order; SOC_SSAO_TILE=0
-    // selects the plain gather kernel (the same bits: tests/test_gpu_parity.py)
-    const bool tiled = tuning_knob("SOC_SSAO_TILE", 1) != 0;
-    if (noise_table && sip && full && tiled) {
-        SsaoParams pt = p;
-        pt.swz = 1;
-        const dim3 g(ceil_div(target.width, kSsaoTX), ceil_div(target.height, kSsaoTY));
-        const int early = tuning_knob("SOC_SSAO_EARLY", 2);
-        // SOC_SSAO_PIPE (default 1): the software-pipelined tap loop (ssao_pipe_kernel; the same bits)
-        // the projection's w row (0, 0, -1, 0) (the reference's perspective; jitter moves only the x / y rows): the
-        // range test's sample depth from the tap's w' (PERSP); SOC_SSAO_PIPE=2 forces the affine form
-        const float* P = pt.proj.m;
-        const int pipe = tuning_knob("SOC_SSAO_PIPE", 1);
-        const bool persp = pipe == 1 && P[3] == 0.0f && P[7] == 0.0f && P[11] == -1.0f && P[15] == 0.0f;
-        if (pipe && persp)
-            launch("ssao_pipe_kernel", kSsaoTileLanes, ssao_pipe_kernel<kSsaoTX, kSsaoTY, kSsaoHalo, true>, g, kSsaoTileLanes, 0, st,
-                   dd, dn, dt, tb, pt);
-        else if (pipe)
-            launch("ssao_pipe_kernel", kSsaoTileLanes, ssao_pipe_kernel<kSsaoTX, kSsaoTY, kSsaoHalo, false>, g, kSsaoTileLanes, 0, st,
-                   dd, dn, dt, tb, pt);
-        else if (early == 1)
-            launch("ssao_lds_kernel", kSsaoTileLanes,
-                   ssao_lds_kernel<true, true, true, kSsaoTX, kSsaoTY, kSsaoHalo, 2, true, 1>, g, kSsaoTileLanes, 0, st, dd,
-                   dn, dt, tb, pt);
-        else if (early == 2)
-            launch("ssao_lds_kernel", kSsaoTileLanes,
-                   ssao_lds_kernel<true, true, true, kSsaoTX, kSsaoTY, kSsaoHalo, 2, true, 2>, g, kSsaoTileLanes, 0, st, dd,
-                   dn, dt, tb, pt);
-        else
-            launch("ssao_lds_kernel", kSsaoTileLanes, ssao_lds_kernel<true, true, true, kSsaoTX, kSsaoTY, kSsaoHalo, 2, true>,
-                   g, kSsaoTileLanes, 0, st, dd, dn, dt, tb, pt);
-    } else if (noise_table && sip && full) SOC_SSAO_LAUNCH(true, true, true);
-    else if (noise_table && sip) SOC_SSAO_LAUNCH(true, true, false);
-    else if (noise_table) SOC_SSAO_LAUNCH(true, false, false);
-    else if (sip && full) SOC_SSAO_LAUNCH(false, true, true);
-    else {
-        // a sparse inverse projection with a partial kernel and no table also lands here: the general kernel's taps
-        // are in texel space, not the sparse path's 1/256-texel steps
-        if (sip) fold_tap_constants(p, depth.width, depth.height, false);
-        SOC_SSAO_LAUNCH(false, false, false);
-    }
-#undef SOC_SSAO_LAUNCH
-    return check_launch("ssao_generation");
+    SsaoPlan pl;
+    const int rc = plan_ssao_generation(g, depth, normal, target, noise_table, pl);
+    return rc ? rc : issue_ssao(pl, stream);
 }
 
 extern "C" int soc_ssao_blur(const soc_globals* g, soc_img ssao, soc_img target, soc_stream stream) {
     (void)g;
-    int rc = check_img(ssao, SOC_FMT_R8_UNORM, "soc_ssao_blur", "ssao");
-    if (!rc) rc = check_img(target, SOC_FMT_R8_UNORM, "soc_ssao_blur", "target");
+    SsaoBlurPlan pl;
+    const int rc = plan_ssao_blur(ssao, target, pl);
     if (rc) return rc;
-    if (ssao.data == target.data) return set_error(SOC_E_INVALID_ARG, "soc_ssao_blur: source and target alias");
-    dim3 blk(64, 4), grd(ceil_div(target.width, 64), ceil_div(target.height, 4));
-    if (ssao.width == target.width && ssao.height == target.height && ssao.width <= 8192 && ssao.height <= 8192)
-        launch("ssao_blur_kernel", kWorkgroup, ssao_blur_kernel, grd, blk, 0, hs(stream), dimg(ssao), dimg(target));
-    else
-        launch("ssao_blur_generic", kWorkgroup, ssao_blur_generic, grd, blk, 0, hs(stream), dimg(ssao), dimg(target), 1.0f / (float)ssao.width,
-                                                       1.0f / (float)ssao.height);
+    const dim3 blk(64, 4), grd(pl.grid_x, pl.grid_y);
+    if (pl.generic) launch("ssao_blur_generic", kWorkgroup, ssao_blur_generic, grd, blk, 0, hs(stream), pl.src, pl.dst, pl.tx, pl.ty);
+    else launch("ssao_blur_kernel", kWorkgroup, ssao_blur_kernel, grd, blk, 0, hs(stream), pl.src, pl.dst);
     return check_launch("ssao_blur");
 }

@@ -135,8 +135,7 @@ extern "C" int soc_screen_space_reflection(const soc_globals* g, soc_img depth, 
                              target.width, target.height);
     }
     // the depth taps address the image with 32-bit byte offsets (soc_device.hpp BufImg)
-    if ((long long)depth.pitch_bytes * depth.height >= (1ll << 31) || depth.pitch_bytes >= (1 << 23))
-        return set_error(SOC_E_SHAPE, "%s: depth image exceeds the 2 GiB buffer-offset range", fn);
+    if (!buffer_range_ok(depth)) return set_error(SOC_E_SHAPE, "%s: depth image exceeds the 2 GiB buffer-offset range", fn);
     SsrParams p;
     p.proj = mat4(g->camera_projection_matrix);
     p.inv_proj = mat4(g->camera_inverse_projection_matrix);

@@ -6,20 +6,12 @@
 // reference graph (renderer.cpp:1182-1198) are removed: the resolved colour ping-pongs between two
 // images owned by the caller, and the current velocity is written to the next frame's velocity
 // history from inside this kernel (velocity_history_out), which saves the separate 16 B/px copy.
-#include "agx.hpp"
-#include "soc_internal.hpp"
+#include "post_plan.hpp"
 
 namespace soc {
 namespace {
 
-struct TaaParams {
-    float rw, rh;       // recip_rn(target extent) for the pixel-centre uv (div_rn)
-    float pox, poy;     // 1 / resolution
-    float accum0;       // min(0.1, frame_counter)
-    int swz;            // XCD-aware tile order (pair path)
-};
-
-constexpr int BX = 64, BY = 4;
+constexpr int BX = kTaaBX, BY = kTaaBY;
 
 __device__ __forceinline__ f4 min4(f4 a, f4 b) { return f4{fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), fminf(a.w, b.w)}; }
 __device__ __forceinline__ f4 max4(f4 a, f4 b) { return f4{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)}; }
@@ -129,15 +121,6 @@ __device__ __forceinline__ v2f gauss_col4(h2 a, h2 b, h2 c) {
 // packed f16 (exact), column-wise and shared by the two pixels; the 3x3 Gaussian is evaluated as
 // column sums (separable weights, different rounding order); the closest-depth texel is chosen with
 // the reference's iteration order and tie rule, exactly.
-// Fused ToneMappingTask (tone_mapping.inl:145-176) epilogue: the resolved RGBA16F pair, exactly as it
-// is stored, goes through the same AgX device function as tonemap_pair into an RGBA8_UNORM image.
-struct TmOut {
-    DImg out;
-    const soc_auto_exposure* ae;
-    TmParams p;
-    int srgb;   // RGBA8_SRGB framebuffer: sRGB-encode on store
-};
-
 // The history taps of pixel k of the pair (0: colour, 1: velocity): the texel pairs (i0, i0 + 1) of rows ay.i0 and
 // ay.i1, one 16-B load per row.
 // The velocity history needs only the RG words of its two texels (words 0 and 2 of the pair): a 12-byte load (the
@@ -423,12 +406,10 @@ __global__ __launch_bounds__(kWorkgroup) void taa_pair2(DImg target, DImg cur, D
 // velocity pair (the fused history copy) from LDS. Per lane about 4 staging loads instead of 9 neighbourhood, velocity
 // and copy loads (the texture path is the kernel's bound), and the velocity gather no longer waits on a load level.
 // The same values reach the same arithmetic (taa_pair_tail) as taa_pair2: the same bits.
-constexpr int kTaaPairs = 64;                                     // output pairs per workgroup row
 constexpr int kTaaTP = kTaaPairs + 2;                             // staged pairs (pair p0 - 1 .. p0 + 64)
 constexpr int kTaaTQ = kTaaPairs / 2 + 2;                         // staged depth quads (quad q0 - 1 .. q0 + 32)
 
-constexpr int kTaaLdsRows = 4;                                   // rows per workgroup: 4 measured against 2 and 8
-constexpr int kTaaLdsLanes = 64 * kTaaLdsRows;                    // (profiles/r03_ab_taa_lds.txt); the launch bound
+constexpr int kTaaLdsLanes = 64 * kTaaLdsRows;                    // the launch bound
 // Image-border copies in the tiles: the staged pair left of the image holds texel 0 twice and the one right of it texel
 // W - 1 twice, the depth quads likewise (and the last quad of a row with W % 4 == 2 has texel W - 1 at column W), so the
 // lanes at a border read their clamped side columns and closest-depth velocity texels from the tiles like every other
@@ -628,108 +609,40 @@ __global__ __launch_bounds__(kWorkgroup) void copy_rows(const char* __restrict__
 using namespace soc;
 
 namespace {
-// tm != nullptr: launch the fused TAA + tone-map kernel if the pair path applies (returns 1 otherwise,
-// having launched nothing)
-int taa_launch(const soc_globals* g, soc_img target, soc_img current_color, soc_img previous_color, soc_img current_velocity,
-               soc_img previous_velocity, soc_img depth, soc_img velocity_history_out, const TmOut* tm, soc_stream stream) {
-    static const char* P = "soc_temporal_antialiasing";
-    if (!g) return set_error(SOC_E_INVALID_ARG, "%s: null globals", P);
-    int rc = check_img(target, SOC_FMT_RGBA16F, P, "target");
-    if (!rc) rc = check_img(current_color, SOC_FMT_RGBA16F, P, "current_color");
-    if (!rc) rc = check_img(previous_color, SOC_FMT_RGBA16F, P, "previous_color");
-    if (!rc) rc = check_img(current_velocity, SOC_FMT_RGBA16F, P, "current_velocity");
-    if (!rc) rc = check_img(previous_velocity, SOC_FMT_RGBA16F, P, "previous_velocity");
-    if (!rc) rc = check_img(depth, SOC_FMT_D32F, P, "depth");
-    if (rc) return rc;
-    if (target.data == current_color.data || target.data == previous_color.data)
-        return set_error(SOC_E_INVALID_ARG, "%s: target aliases an input", P);
-    if (velocity_history_out.data) {
-        rc = check_img(velocity_history_out, SOC_FMT_RGBA16F, P, "velocity_history_out");
-        if (rc) return rc;
-        if (velocity_history_out.data == previous_velocity.data || velocity_history_out.data == current_velocity.data)
-            return set_error(SOC_E_INVALID_ARG, "%s: velocity_history_out aliases a velocity input", P);
-        if (velocity_history_out.width != current_velocity.width || velocity_history_out.height != current_velocity.height)
-            return set_error(SOC_E_SHAPE, "%s: velocity_history_out extent != current_velocity extent", P);
-    }
-    TaaParams p;
-    p.rw = recip_rn(target.width);
-    p.rh = recip_rn(target.height);
-    p.pox = 1.0f / (float)g->resolution[0];
-    p.poy = 1.0f / (float)g->resolution[1];
-    p.accum0 = fminf(0.1f, (float)g->frame_counter);
-    p.swz = -16;   // XCD vertical bands of 16-tile strips: HBM traffic 1.39x -> 1.01x algorithmic
-    const int W = target.width, H = target.height;
-    auto same = [&](const soc_img& im) { return im.width == W && im.height == H; };
-    const bool fast = W == g->resolution[0] && H == g->resolution[1] && same(current_color) && same(depth) &&
-                      same(current_velocity) && W <= 8192 && H <= 8192;
-    dim3 blk(BX, BY), grd(ceil_div(W, BX), ceil_div(H, BY));
-    DImg vo = velocity_history_out.data ? dimg(velocity_history_out) : DImg{nullptr, 0, 0, 0};
-    auto a16 = [](const soc_img& im) { return (reinterpret_cast<uintptr_t>(im.data) & 15u) == 0 && (im.pitch_bytes & 15) == 0; };
-    // the pair kernels address the staged images (and the depth quads through a buffer resource) with 32-bit offsets
-    // (a signed 24-bit row x pitch product)
-    auto buf_ok = [](const soc_img& im) { return (long long)im.pitch_bytes * im.height < (1ll << 31) && im.pitch_bytes < (1 << 23); };
-    const bool pair = fast && W % 2 == 0 && a16(target) && a16(current_color) && a16(current_velocity) &&
-                      (reinterpret_cast<uintptr_t>(depth.data) & 7u) == 0 && (depth.pitch_bytes & 7) == 0 &&
-                      (!velocity_history_out.data || a16(velocity_history_out)) && previous_color.width >= 2 &&
-                      previous_velocity.width == previous_color.width && previous_velocity.height == previous_color.height &&
-                      buf_ok(current_color) && buf_ok(current_velocity) && buf_ok(depth);
-    if (tm && !pair) return 1;
-    if (pair) {
-        // 32 x 8 lanes (64 x 8 pixels): the 3-row neighbourhood reloads 10 rows per 8 instead of 6 per 4
-        const int by = 8, bxl = 256 / by;
-        dim3 blk(bxl, by), g2(ceil_div(W / 2, bxl), ceil_div(H, by));
-        // neighbourhood source: 3 = LDS-staged tiles (default; needs a 16-B aligned depth image), 2 = halo lanes, 1 = lane
-        // shifts + edge-lane loads, 0 = every lane loads its side columns (the same bits, tests/test_gpu_parity.py)
-        const int nbr = tuning_knob("SOC_TAA_NBR", 4);
-        const dim3 blk_h(64, 4), g2_h(ceil_div(W / 2, 62), ceil_div(H, 4));
-        if (nbr == 4 && a16(depth)) {
-            const dim3 gl(ceil_div(W / 2, kTaaPairs), ceil_div(H, 4));
-            if (tm)
-                launch("taa_lds", kTaaLdsLanes, taa_lds<true, kTaaLdsRows, true>, gl, blk_h, 0, hs(stream), dimg(target),
-                       dimg(current_color), dimg(previous_color), dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo,
-                       p, *tm);
-            else
-                launch("taa_lds", kTaaLdsLanes, taa_lds<false, kTaaLdsRows, true>, gl, blk_h, 0, hs(stream), dimg(target),
-                       dimg(current_color), dimg(previous_color), dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo,
-                       p, TmOut{});
-        } else if (nbr == 3 && a16(depth)) {
-            const dim3 gl(ceil_div(W / 2, kTaaPairs), ceil_div(H, 4));
-            if (tm)
-                launch("taa_lds", kTaaLdsLanes, taa_lds<true>, gl, blk_h, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                          dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p, *tm);
-            else
-                launch("taa_lds", kTaaLdsLanes, taa_lds<false>, gl, blk_h, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                           dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p,
-                                                           TmOut{});
-        } else if (tm && nbr >= 2)
-            launch("taa_pair2", kWorkgroup, taa_pair2<true, 2>, g2_h, blk_h, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                       dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p, *tm);
-        else if (tm && nbr == 0)
-            launch("taa_pair2", kWorkgroup, taa_pair2<true, 0>, g2, blk, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                       dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p, *tm);
-        else if (tm)
-            launch("taa_pair2", kWorkgroup, taa_pair2<true, 1>, g2, blk, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                       dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p, *tm);
-        else
-            launch("taa_pair2", kWorkgroup, taa_pair2<false, 2>, g2_h, blk_h, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                        dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p,
-                                                        TmOut{});
-    } else if (fast)
-        launch("taa_fast", kWorkgroup, taa_fast, grd, blk, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color), dimg(current_velocity),
-                                              dimg(previous_velocity), dimg(depth), vo, p);
+// The plan's kernel on `stream`: each instantiation is named here once; a form without an entry is SOC_E_INVALID_ARG.
+int issue_taa(const TaaPlan& pl, soc_stream stream) {
+    using Pair = void (*)(DImg, DImg, DImg, DImg, DImg, DImg, DImg, TaaParams, TmOut);
+    static const Pair pairs[2][kTaaFast] = {
+        {taa_lds<false, kTaaLdsRows, true>, taa_lds<false>, nullptr, nullptr, taa_pair2<false, 2>},
+        {taa_lds<true, kTaaLdsRows, true>, taa_lds<true>, taa_pair2<true, 0>, taa_pair2<true, 1>, taa_pair2<true, 2>}};
+    static const char* const names[kTaaKernels] = {"taa_lds", "taa_lds", "taa_pair2", "taa_pair2", "taa_pair2", "taa_fast", "taa_generic"};
+    if (pl.kernel < 0 || pl.kernel >= kTaaKernels || (pl.kernel < kTaaFast ? !pairs[pl.tm][pl.kernel] : pl.tm))
+        return set_error(SOC_E_INVALID_ARG, "temporal_antialiasing: no kernel of form %d, tm %d", (int)pl.kernel, (int)pl.tm);
+    const dim3 grd(pl.grid_x, pl.grid_y), blk(pl.block_x, pl.block_y);
+    const DImg* im = pl.img;
+    if (pl.kernel < kTaaFast)
+        launch(names[pl.kernel], pl.kernel <= kTaaLds ? kTaaLdsLanes : kWorkgroup, pairs[pl.tm][pl.kernel], grd, blk, 0, hs(stream),
+               im[0], im[1], im[2], im[3], im[4], im[5], im[6], pl.p, pl.tmo);
     else
-        launch("taa_generic", kWorkgroup, taa_generic, grd, blk, 0, hs(stream), dimg(target), dimg(current_color), dimg(previous_color),
-                                                 dimg(current_velocity), dimg(previous_velocity), dimg(depth), vo, p);
+        launch(names[pl.kernel], kWorkgroup, pl.kernel == kTaaFast ? taa_fast : taa_generic, grd, blk, 0, hs(stream), im[0], im[1],
+               im[2], im[3], im[4], im[5], im[6], pl.p);
     return check_launch("temporal_antialiasing");
 }
-
 }  // namespace
+
+int soc::temporal_antialiasing(const TaaCall& c, soc_stream stream) {
+    TaaPlan pl;
+    int rc = plan_taa(c, pl);
+    if (!rc) rc = issue_taa(pl, stream);
+    if (!rc && pl.tone_mapping_pass) rc = soc_tone_mapping(c.g, c.target, c.ae, c.output, stream);
+    return rc;
+}
 
 extern "C" int soc_temporal_antialiasing(const soc_globals* g, soc_img target, soc_img current_color, soc_img previous_color,
                                          soc_img current_velocity, soc_img previous_velocity, soc_img depth,
                                          soc_img velocity_history_out, soc_stream stream) {
-    return taa_launch(g, target, current_color, previous_color, current_velocity, previous_velocity, depth,
-                      velocity_history_out, nullptr, stream);
+    return temporal_antialiasing({g, target, current_color, previous_color, current_velocity, previous_velocity, depth,
+                                  velocity_history_out, false, nullptr, soc_img{}}, stream);
 }
 
 extern "C" int soc_temporal_antialiasing_tone_mapping(const soc_globals* g, soc_img target, soc_img current_color,
@@ -737,33 +650,8 @@ extern "C" int soc_temporal_antialiasing_tone_mapping(const soc_globals* g, soc_
                                                       soc_img previous_velocity, soc_img depth, soc_img velocity_history_out,
                                                       const soc_auto_exposure* d_auto_exposure, soc_img output,
                                                       soc_stream stream) {
-    static const char* P = "soc_temporal_antialiasing_tone_mapping";
-    if (!g || !d_auto_exposure) return set_error(SOC_E_INVALID_ARG, "%s: null globals / auto exposure buffer", P);
-    int rc = check_img(output, 0, P, "output");
-    if (rc) return rc;
-    const bool fusable = (output.format == SOC_FMT_RGBA8_UNORM || output.format == SOC_FMT_RGBA8_SRGB) &&
-                         output.width == target.width &&
-                         output.height == target.height && (reinterpret_cast<uintptr_t>(output.data) & 7u) == 0 &&
-                         (output.pitch_bytes & 7) == 0 && output.data != target.data;
-    if (fusable) {
-        TmOut tm;
-        tm.out = dimg(output);
-        tm.ae = d_auto_exposure;
-        tm.srgb = output.format == SOC_FMT_RGBA8_SRGB;
-        agx_matrices(g->compression, tm.p.M.m, tm.p.Minv.m);
-        tm.p.linear = g->agxDs_linear_section;
-        tm.p.peak = g->peak;
-        tm.p.saturation = g->saturation;
-        tm_params_finish(tm.p);
-        rc = taa_launch(g, target, current_color, previous_color, current_velocity, previous_velocity, depth,
-                        velocity_history_out, &tm, stream);
-        if (rc <= 0) return rc;   // launched (or failed validation)
-    }
-    // not fusable: the two passes back to back (same results)
-    rc = taa_launch(g, target, current_color, previous_color, current_velocity, previous_velocity, depth,
-                    velocity_history_out, nullptr, stream);
-    if (rc) return rc;
-    return soc_tone_mapping(g, target, d_auto_exposure, output, stream);
+    return temporal_antialiasing({g, target, current_color, previous_color, current_velocity, previous_velocity, depth,
+                                  velocity_history_out, true, d_auto_exposure, output}, stream);
 }
 
 extern "C" int soc_copy_image(soc_img target, soc_img source, soc_stream stream) {
@@ -773,8 +661,7 @@ extern "C" int soc_copy_image(soc_img target, soc_img source, soc_stream stream)
     if (target.format != source.format || target.width != source.width || target.height != source.height)
         return set_error(SOC_E_SHAPE, "soc_copy_image: format/extent mismatch");
     const int row_bytes = source.width * bytes_per_pixel(source.format);
-    const bool vec = ((reinterpret_cast<uintptr_t>(source.data) | reinterpret_cast<uintptr_t>(target.data)) & 15u) == 0 &&
-                     (source.pitch_bytes & 15) == 0 && (target.pitch_bytes & 15) == 0;
+    const bool vec = aligned_to(source, 16) && aligned_to(target, 16);
     if (!vec) {
         hipError_t e = hipMemcpy2DAsync(target.data, target.pitch_bytes, source.data, source.pitch_bytes, row_bytes,
                                         source.height, hipMemcpyDeviceToDevice, hs(stream));

@@ -5,7 +5,7 @@ usage: python tools/isa_by_kernel.py PARENT.s BRANCH.s     (each from hipcc ... 
 The compiler emits kernels in the order the host code first names them, numbers labels (.LBB<n>_, .Lfunc_end<n>) and
 loop-header comments by that order and pads a label's comment to a column; a launcher that names the same instantiations
 elsewhere therefore gives another file with the same kernels. This splits both files at the kernels' sections and their
-metadata entries, replaces the mangled soc:: symbols and those order-dependent numbers, sorts by demangled name (the
+metadata entries, replaces the mangled soc:: symbols and those order-dependent numbers, drops the trailer after the last kernel, sorts by demangled name (the
 anonymous namespace dropped) and compares each kernel's text and its metadata entry (registers, LDS, kernarg layout).
 One line per kernel with a hash; exit status 1 when a kernel differs or the sets differ."""
 import hashlib
@@ -23,6 +23,7 @@ def norm(text):
     text = re.sub(r"_ZN3soc[A-Za-z0-9_.$]*", "SOC_SYMBOL", text)
     text = re.sub(r"\.LBB\d+_", ".LBB_", text)
     text = re.sub(r"Header=BB\d+_", "Header=BB_", text)   # the function's index in comments
+    text = re.sub(r"(Child|Parent) Loop BB\d+_", r"\1 Loop BB_", text)
     text = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", text)
     return re.sub(r"(?m)^(\.LBB_\d+:)[ \t]+;", r"\1 ;", text)   # the comment column follows the label's width
 
@@ -40,7 +41,8 @@ def split(path):
     chunks = {}
     for k, s in enumerate(starts):
         e = starts[k + 1] if k + 1 < len(starts) else len(body)
-        chunks[syms[k]] = "\n".join(body[s:e])
+        # the kernel emitted last carries the file's trailer (the code's end padding, register maximums, the cuid object)
+        chunks[syms[k]] = re.split(r"\n(?:\t\.text\n\t\.p2alignl 6, \d+\n\t\.fill 256, 4, \d+\n)?\t\.section\t\.AMDGPU\.gpr_maximums", "\n".join(body[s:e]))[0]
     head = "\n".join(body[:starts[0]])
     # metadata entries: each starts at "  - .agpr_count:" (first key of a kernel entry, keys sorted)
     ms = [i for i, l in enumerate(md) if re.match(r"  - \.\w+", l)]
@@ -50,7 +52,7 @@ def split(path):
         ent = md[s:e]
         name = next(re.search(r"(_Z\w+)", l).group(1) for l in ent if ".name:" in l and "_Z" in l)
         # the last entry carries the file's trailer
-        mchunks[name] = "\n".join(ent)
+        mchunks[name] = "\n".join(ent).split("\namdhsa.target:")[0]
     names = demangle(syms)
     out = {}
     for sym, n in zip(syms, names):

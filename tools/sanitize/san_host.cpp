@@ -1,6 +1,6 @@
 // san_host — drives the host code under AddressSanitizer + UndefinedBehaviorSanitizer (tools/sanitize/Makefile).
 // No GPU call is made: the globals feed and ECS scene feed, ABI introspection, the render graph (construction,
-// caller passes, derived and ring dependencies, raster head, error paths), the clouds and Composition planners, the raster workspaces and
+// caller passes, derived and ring dependencies, raster head, error paths), the clouds, Composition, TAA, SSAO and bloom planners, the raster workspaces and
 // the draw scenes' host checks, the PNG / EXR writers, the scene synthesiser, and every pass of the CPU oracle on small
 // images (odd extents included). Exit 0 when every check passes; a sanitizer report aborts the run
 // (-fno-sanitize-recover).
@@ -35,6 +35,9 @@ int64_t soc_debug_plan_composition(const soc_globals* g, const soc_globals* d_gl
                                    soc_auto_exposure* ae, uint32_t* scratch, const soc_img* mip1, const soc_img* mip3,
                                    const void* d_bounds, uint32_t light_flags, uint32_t* d_shaded,
                                    const soc_sun_cascades* cascades, char* buf, size_t cap);
+// test hook of the TAA, SSAO and bloom planners (csrc/post_plan.cpp), not in the public header
+int64_t soc_debug_plan_post(int32_t pass, const soc_globals* g, const soc_img* images, int32_t n_images, const void* aux,
+                            int32_t arg, const int32_t* resident, char* buf, size_t cap);
 }
 
 namespace {
@@ -390,6 +393,214 @@ void composition_plan(const soc_globals& g0) {
     }
 }
 
+// The TAA, SSAO and bloom planners through their test hook (no GPU call; fake, never dereferenced addresses): the
+// accepted cases of tests/test_post_plan.py (every kernel family, the extents, the views and the tone-map outputs), every
+// rejection of the entry points, a truncated buffer and the length-only call.
+void post_plans(const soc_globals& g0) {
+    enum { TAA, TAA_TM, SSAO, SSAO_BLUR, SSAO_NOISE, BLOOM_W, BLOOM_DOWN, BLOOM_UP, SPARSE = 256 };
+    char* fake = reinterpret_cast<char*>(0x10000000);
+    const void* aux = fake + 0xc1000000u;
+    const int32_t resident[6] = {24, 24, 24, 24, 24, 24};
+    soc_globals g = g0;
+    char buf[2048];
+    auto image = [&](int i, int w, int h, int fmt) {
+        const int bpp = fmt == SOC_FMT_RGBA16F ? 8 : fmt == SOC_FMT_R8_UNORM ? 1 : 4;
+        return soc_img{fake + ((size_t)i << 28), w, h, w * bpp, fmt};
+    };
+    auto has = [&](const char* text) { return std::strstr(buf, text) != nullptr; };
+    auto plan = [&](int pass, const soc_img* im, int n, int arg = 0, const void* a = nullptr, const soc_globals* gl = nullptr) {
+        return soc_debug_plan_post(pass, gl ? gl : &g, im, n, a, arg, resident, buf, sizeof buf);
+    };
+    // TAA: target, colour, history, velocity, velocity history, depth, velocity_history_out, output
+    struct Taa { soc_img im[8]; };
+    auto taa = [&](int W, int H) {
+        Taa t;
+        for (int i = 0; i < 8; ++i) t.im[i] = image(i, W, H, i == 5 ? SOC_FMT_D32F : i == 7 ? SOC_FMT_RGBA8_UNORM : SOC_FMT_RGBA16F);
+        g.resolution[0] = W;
+        g.resolution[1] = H;
+        return t;
+    };
+    for (int tm = 0; tm < 2; ++tm) {
+        const void* ae = tm ? aux : nullptr;
+        const int n = 7 + tm;
+        const int sizes[6][2] = {{64, 36}, {130, 58}, {97, 55}, {8192, 16}, {8194, 16}, {64, 256}};
+        // 130 depth texels a row are no multiple of 16 bytes: the halo-lane pair kernel
+        const char* kernel[6] = {"taa_lds", "taa_pair2", "taa_fast", "taa_lds", "taa_generic", "taa_lds"};
+        for (int k = 0; k < 6; ++k) {
+            Taa t = taa(sizes[k][0], sizes[k][1]);
+            expect(plan(tm, t.im, n, 0, ae) > 0 && has(kernel[k]) && has("pass\ttone_mapping") == (tm && (k == 2 || k == 4)),
+                   "post plan: TAA extents");
+        }
+        Taa t = taa(64, 36);
+        Taa v = t;
+        v.im[5].data = fake + (5u << 28) + 8;   // a depth base 8 bytes off
+        expect(plan(tm, v.im, n, 0, ae) > 0 && has("taa_pair2\t") && has("nbr=2"), "post plan: TAA depth offset");
+        for (int i : {0, 1, 3, 6}) {   // each misaligned in turn
+            v = t;
+            v.im[i].data = fake + ((size_t)i << 28) + 8;
+            expect(plan(tm, v.im, n, 0, ae) > 0 && has("taa_fast"), "post plan: TAA misaligned view");
+        }
+        v = t;
+        v.im[1].width = v.im[1].height = 18;   // another colour extent
+        v.im[1].pitch_bytes = 18 * 8;
+        expect(plan(tm, v.im, n, 0, ae) > 0 && has("taa_generic"), "post plan: TAA generic");
+        v = t;
+        v.im[1].pitch_bytes = 1 << 23;   // past the pair kernels' 32-bit offsets
+        expect(plan(tm, v.im, n, 0, ae) > 0 && has("taa_fast"), "post plan: TAA range");
+        v = t;
+        v.im[6] = soc_img{};
+        expect(plan(tm, v.im, n, 0, ae) > 0 && has("vel_out=0"), "post plan: TAA without velocity_history_out");
+        for (uint32_t fc : {0u, 5u}) {
+            g.frame_counter = fc;
+            expect(plan(tm, t.im, n, 0, ae) > 0, "post plan: TAA frame counter");
+        }
+        // rejections
+        expect(soc_debug_plan_post(tm, nullptr, t.im, n, ae, 0, resident, buf, sizeof buf) == SOC_E_INVALID_ARG, "post plan: TAA null globals");
+        for (int i = 0; i < 7; ++i) {
+            v = t;
+            v.im[i].format = SOC_FMT_R8_UNORM;
+            expect(plan(tm, v.im, n, 0, ae) == SOC_E_INVALID_ARG, "post plan: TAA image format");
+        }
+        for (int i : {1, 2}) {
+            v = t;
+            v.im[i].data = t.im[0].data;
+            expect(plan(tm, v.im, n, 0, ae) == SOC_E_INVALID_ARG, "post plan: TAA target aliases an input");
+        }
+        for (int i : {3, 4}) {
+            v = t;
+            v.im[6].data = t.im[i].data;
+            expect(plan(tm, v.im, n, 0, ae) == SOC_E_INVALID_ARG, "post plan: TAA velocity_history_out aliases");
+        }
+        v = t;
+        v.im[6].width = 32;
+        expect(plan(tm, v.im, n, 0, ae) == SOC_E_SHAPE, "post plan: TAA velocity_history_out extent");
+        if (tm) {
+            expect(plan(TAA_TM, t.im, 8, 0, nullptr) == SOC_E_INVALID_ARG, "post plan: TAA null auto exposure");
+            const int fmts[3] = {SOC_FMT_RGBA8_SRGB, SOC_FMT_RGBA16F, SOC_FMT_RGBA8_UNORM};
+            for (int k = 0; k < 3; ++k) {
+                v = t;
+                v.im[7] = image(7, 64, 36, fmts[k]);
+                expect(plan(TAA_TM, v.im, 8, 0, ae) > 0 && has("tm=1 sf=1") == (k != 1) && has("pass\t") == (k == 1), "post plan: TAA output format");
+            }
+            v = t;
+            v.im[7].data = fake + (7u << 28) + 4;
+            expect(plan(TAA_TM, v.im, 8, 0, ae) > 0 && has("pass\ttone_mapping"), "post plan: TAA misaligned output");
+            v.im[7] = t.im[0];   // aliases the target: two passes
+            expect(plan(TAA_TM, v.im, 8, 0, ae) > 0 && has("pass\ttone_mapping"), "post plan: TAA output aliases the target");
+            v.im[7].width = 0;
+            expect(plan(TAA_TM, v.im, 8, 0, ae) == SOC_E_INVALID_ARG, "post plan: TAA bad output");
+        }
+        expect(soc_debug_plan_post(tm, &g, t.im, n, ae, 0, resident, buf, 16) > 16 && std::strlen(buf) == 15, "post plan: truncated");
+        expect(soc_debug_plan_post(tm, &g, t.im, n, ae, 0, resident, nullptr, 0) > 0, "post plan: length only");
+        expect(soc_debug_plan_post(tm, &g, t.im, n - 1, ae, 0, resident, buf, sizeof buf) == SOC_E_INVALID_ARG, "post plan: too few images");
+    }
+    expect(soc_debug_plan_post(8, &g, nullptr, 0, nullptr, 0, resident, buf, sizeof buf) == SOC_E_INVALID_ARG, "post plan: unknown pass");
+    // SSAO: depth, normal, target
+    const int frames[3][2] = {{128, 72}, {260, 130}, {97, 55}};
+    for (int k = 0; k < 3; ++k)
+        for (int table = 0; table < 2; ++table) {
+            const int W = frames[k][0], H = frames[k][1];
+            soc_img im[3] = {image(0, W, H, SOC_FMT_D32F), image(1, W, H, SOC_FMT_RGBA16F), image(2, W / 2, H / 2, SOC_FMT_R8_UNORM)};
+            g = g0;
+            expect(plan(SSAO, im, 3, 0, table ? aux : nullptr) > 0 && has(table ? "ssao_pipe_kernel" : "ssao_kernel\ttable=0 sip=1 full=1"),
+                   "post plan: SSAO generation");
+            for (int ks : {8, 40}) {
+                g.ssao_kernel_size = ks;
+                expect(plan(SSAO, im, 3, 0, table ? aux : nullptr) > 0 && has(ks == 40 ? (table ? "ssao_pipe_kernel" : "full=1") : "full=0"),
+                       "post plan: SSAO kernel size");
+            }
+            g = g0;
+            g.camera_projection_matrix[11] = -0.5f;
+            expect(plan(SSAO, im, 3, 0, table ? aux : nullptr) > 0 && has("persp=1") == false, "post plan: SSAO projection w row");
+            g = g0;
+            g.camera_inverse_projection_matrix[2] = 0.125f;
+            expect(plan(SSAO, im, 3, 0, table ? aux : nullptr) > 0 && has("sip=0"), "post plan: SSAO dense inverse projection");
+            g = g0;
+            g.ssao_radius = 0.0f;
+            expect(plan(SSAO, im, 3, 0, table ? aux : nullptr) > 0 && has("sip=0"), "post plan: SSAO radius 0");
+            g = g0;
+            soc_img bad[3] = {im[0], im[1], im[2]};
+            bad[0].width = bad[0].height = 1;
+            bad[0].pitch_bytes = 4;
+            expect(plan(SSAO, bad, 3, 0, aux) == SOC_E_SHAPE, "post plan: SSAO depth 1x1");
+            bad[0] = im[0];
+            bad[0].pitch_bytes = 1 << 23;
+            expect(plan(SSAO, bad, 3, 0, aux) == SOC_E_SHAPE, "post plan: SSAO range");
+            for (int i = 0; i < 3; ++i) {
+                soc_img b2[3] = {im[0], im[1], im[2]};
+                b2[i].format = SOC_FMT_RGBA8_UNORM;
+                expect(plan(SSAO, b2, 3, 0, aux) == SOC_E_INVALID_ARG, "post plan: SSAO image format");
+            }
+            expect(soc_debug_plan_post(SSAO, nullptr, im, 3, aux, 0, resident, buf, sizeof buf) == SOC_E_INVALID_ARG, "post plan: SSAO null globals");
+            soc_img blur[2] = {im[2], image(3, W / 2, H / 2, SOC_FMT_R8_UNORM)};
+            expect(plan(SSAO_BLUR, blur, 2) > 0 && has("ssao_blur_kernel"), "post plan: SSAO blur");
+            blur[1] = image(3, W, H, SOC_FMT_R8_UNORM);
+            expect(plan(SSAO_BLUR, blur, 2) > 0 && has("ssao_blur_generic"), "post plan: SSAO blur, unequal extents");
+            blur[1] = blur[0];
+            expect(plan(SSAO_BLUR, blur, 2) == SOC_E_INVALID_ARG, "post plan: SSAO blur aliased");
+            blur[1].format = SOC_FMT_D32F;
+            expect(plan(SSAO_BLUR, blur, 2) == SOC_E_INVALID_ARG, "post plan: SSAO blur format");
+            soc_img noise[2] = {im[1], im[2]};
+            expect(plan(SSAO_NOISE, noise, 2, 0, aux) > 0 && has("ssao_noise_kernel"), "post plan: SSAO noise");
+            expect(plan(SSAO_NOISE, noise, 2, 0, nullptr) == SOC_E_INVALID_ARG, "post plan: SSAO noise null table");
+            noise[1].height = 0;
+            expect(plan(SSAO_NOISE, noise, 2, 0, aux) == SOC_E_INVALID_ARG, "post plan: SSAO noise extents");
+        }
+    // weighted bloom: emissive, output, four mips
+    const int extents[2][2] = {{64, 48}, {200, 104}};
+    for (int k = 0; k < 2; ++k) {
+        const int W = extents[k][0], H = extents[k][1];
+        soc_img im[6] = {image(0, W, H, SOC_FMT_RGBA16F), image(1, W, H, SOC_FMT_RGBA16F)};
+        for (int i = 0; i < 4; ++i) im[2 + i] = image(2 + i, W >> i, H >> i, SOC_FMT_RGBA16F);
+        for (int stage = 0; stage <= 4; ++stage)
+            for (int r : {8, 24, 4096}) {
+                const int32_t res[6] = {r, r, r, r, r, r};
+                expect(soc_debug_plan_post(BLOOM_W, &g, im, 6, nullptr, stage, res, buf, sizeof buf) > 0 &&
+                           has("bloomw_down01p") == (stage <= 1) && has("bloomw_up10r") == (stage == 0 || stage == 4), "post plan: bloom stages");
+            }
+        expect(plan(BLOOM_W, im, 6, 4 | SPARSE) > 0 && has("zs=1 sparse=1"), "post plan: sparse bloom output");
+        expect(soc_debug_plan_post(BLOOM_W, &g, im, 6, nullptr, 1, nullptr, buf, sizeof buf) == SOC_E_INVALID_ARG, "post plan: bloom null resident sets");
+        expect(plan(BLOOM_W, im, 6, 5) == SOC_E_INVALID_ARG, "post plan: bloom stage");
+        expect(plan(BLOOM_W, im, 2, 0) == SOC_E_INVALID_ARG, "post plan: bloom null mips");
+        expect(plan(BLOOM_W, im, 5, 0) == SOC_E_UNSUPPORTED, "post plan: bloom three mips");
+        soc_img bad[6];
+        for (int i = 0; i < 6; ++i) {
+            std::memcpy(bad, im, sizeof bad);
+            bad[i].format = SOC_FMT_RGBA8_UNORM;
+            expect(plan(BLOOM_W, bad, 6, 0) == SOC_E_INVALID_ARG, "post plan: bloom image format");
+        }
+        std::memcpy(bad, im, sizeof bad);
+        bad[1].data = im[3].data;
+        expect(plan(BLOOM_W, bad, 6, 0) == SOC_E_INVALID_ARG && plan(BLOOM_W, bad, 6, 2) > 0, "post plan: bloom output aliases mip 1");
+        std::memcpy(bad, im, sizeof bad);
+        bad[5].height += 1;
+        expect(plan(BLOOM_W, bad, 6, 0) == SOC_E_UNSUPPORTED, "post plan: bloom chain that does not halve");
+        // per-pass: same extent, exact half, other, forced generic; both sides of the quad bound
+        for (int up = 0; up < 2; ++up) {
+            const int pass = up ? BLOOM_UP : BLOOM_DOWN;
+            const soc_img hi = im[2], same = image(6, W, H, SOC_FMT_RGBA16F), half = im[3], other = image(6, W / 2 + 1, H / 2, SOC_FMT_RGBA16F);
+            soc_img p[2] = {hi, same};
+            expect(plan(pass, p, 2) > 0 && has(up ? "bloom_up_same_q" : "bloom_down_same_q"), "post plan: bloom pass, same extent");
+            expect(plan(pass, p, 2, 1) > 0 && has("_generic"), "post plan: bloom pass, forced generic");
+            p[up ? 1 : 0] = hi;
+            p[up ? 0 : 1] = half;
+            expect(plan(pass, p, 2) > 0 && has(up ? "bloom_up_double\t" : "bloom_down_half_w"), "post plan: bloom pass, exact half");
+            p[up ? 0 : 1] = other;
+            expect(plan(pass, p, 2) > 0 && has("_generic"), "post plan: bloom pass, other ratio");
+            p[1] = p[0];
+            expect(plan(pass, p, 2) == SOC_E_INVALID_ARG, "post plan: bloom pass aliased");
+            p[1] = same;
+            p[1].format = SOC_FMT_D32F;
+            expect(plan(pass, p, 2) == SOC_E_INVALID_ARG, "post plan: bloom pass format");
+        }
+    }
+    soc_img q[2] = {image(0, 512, 512, SOC_FMT_RGBA16F), image(1, 1024, 1024, SOC_FMT_RGBA16F)};
+    expect(plan(BLOOM_UP, q, 2) > 0 && has("bloom_up_double_q"), "post plan: the quad upsample at 2^20 pixels");
+    q[0].height = 511;
+    q[1].height = 1022;
+    expect(plan(BLOOM_UP, q, 2) > 0 && has("bloom_up_double\t"), "post plan: one pixel per lane below it");
+}
+
 void writers(int W, int H) {
     HostImg rgba(W, H, SOC_FMT_RGBA8_UNORM, 4, 200);
     HostImg half(W, H, SOC_FMT_RGBA16F, 8);
@@ -684,6 +895,7 @@ int main() {
         render_graph(g, W, H);
         clouds_plan(g, W, H);
         composition_plan(g);
+        post_plans(g);
         writers(W, H);
         oracle_frame(g, W, H);
         oracle_raster(g, W, H);
